@@ -14,8 +14,14 @@ every N, so the 1/2/4/8-GPU lines divide the same step) whose gradients accumula
 / adds straight into them), followed with --gpus N>1 (torchrun, one rank per GPU, RCCL) by ONE
 all-reduce of that bucket (view-parallel data parallelism, weak scaling).
 
-Output: one JSON line (rank 0) with the metric, a per-kernel HIP-event breakdown, the roofline of
-the dominant kernel and the CPU oracle baseline timed on this host.
+A plain run sets up, warms up, times --steps steps (one region), writes the last step's outputs if
+--dump-outputs DIR is given and prints the headline.  --full also runs every secondary measurement
+(five timed regions with `value` their median, workload counters, sustained and one-stream rates,
+the per-kernel event pass and rooflines, render-only, batch-1, HIP graph, kNN, train step,
+view-parallel training and the CPU oracle baseline timed on this host).
+
+Output: one JSON line (rank 0) with the metric; with --full also a per-kernel HIP-event breakdown,
+the roofline of the dominant kernel, the CPU oracle baseline and the other secondary figures.
 """
 from __future__ import annotations
 
@@ -146,9 +152,19 @@ def main():
     ap.add_argument("--step-events", action="store_true",
                     help="diagnostic: record a HIP event after every timed step (no host syncs) and report the "
                          "per-step times of the timed region in deciles")
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement (workload counters, sustained "
+                         "and one-stream rates, per-kernel event pass and roofline, render-only, batch-1, HIP graph, "
+                         "kNN, train step, view-parallel training, CPU oracle baseline) and report them in the line; "
+                         "without it the run only sets up, warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (every view's image and "
+                         "radii, the parameters' gradients) as DIR/<name>.npy in float32; outputs too large for "
+                         "64 MB in all are written as a fixed seeded sample (see dump_outputs)")
+    ap.add_argument("--regions", type=int, default=None,
                     help="timed regions of --steps steps each; `value` is the median region's rate, every "
-                         "region's rate is reported (`regions_iters_s`)")
+                         "region's rate is reported (`regions_iters_s`); default 1 (--steps is the number of timed "
+                         "steps), 5 with --full")
     ap.add_argument("--sustain-s", type=float, default=2.0,
                     help="after the timed steps, keep stepping for this long (untimed for `value`) and report "
                          "the sustained rate too")
@@ -250,18 +266,23 @@ def main():
 
     streams = [torch.cuda.Stream(dev) for _ in range(max(1, args.streams))]
 
-    def view_fn(r, pre=None):
+    # --dump-outputs: view k's (image, radii) of the latest step (references only: no copy, no sync)
+    last_views = {} if args.dump_outputs else None
+
+    def view_fn(r, pre=None, k=0):
         def run():
             # a fresh screen-space carrier per render, as the reference's render() makes
             # (gaussian_renderer/__init__.py:24); the rasterizer never reads its values (only its
             # .grad is written), so it is not zero-filled; its gradient is not kept here
             m2 = torch.empty_like(params[0], requires_grad=True)
-            img, _ = r(means3D=params[0], means2D=m2, opacities=params[2], shs=params[1], scales=params[3],
-                       rotations=params[4], prepared=pre)
+            img, radii = r(means3D=params[0], means2D=m2, opacities=params[2], shs=params[1], scales=params[3],
+                           rotations=params[4], prepared=pre)
             img.backward(dpix)
+            if last_views is not None:
+                last_views[k] = (img.detach(), radii)
         return run
 
-    view_fns = [view_fn(r) for r in rasts]
+    view_fns = [view_fn(r, k=k) for k, r in enumerate(rasts)]
     fused_front = not args.no_fused_front and len(rasts) > 1
 
     def step(sts=streams):
@@ -272,7 +293,7 @@ def main():
             # view's depth order on its stream; then every view's binning, render and backward
             pre = prepare_views(rasts, params[0], params[2], shs=params[1], scales=params[3], rotations=params[4],
                                 streams=[sts[k % len(sts)] for k in range(len(rasts))])
-            fns = [view_fn(r, p) for r, p in zip(rasts, pre)]
+            fns = [view_fn(r, p, k) for k, (r, p) in enumerate(zip(rasts, pre))]
         # this rank's views, round-robin over the streams: gradients accumulate in the bucket
         vp.run_views(fns, sts)
         if world > 1:
@@ -280,22 +301,23 @@ def main():
         else:
             bucket.finalize()
 
-    # workload counters (one extra forward, untimed)
-    e = torch.Tensor([])
-    num_rendered, _, radii, geom_b, bin_b, img_b = _C.rasterize_gaussians(
-        settings.bg, d.means3D, e, d.opacities, d.scales, d.rotations, 1.0, e, settings.viewmatrix,
-        settings.projmatrix, settings.tanfovx, settings.tanfovy, H, W, d.shs, deg, settings.campos, False, False)
-    visible = int((radii > 0).sum())
-    tiles = ((W + 15) // 16) * ((H + 15) // 16)
-    # instances the render walks reach: per tile min(largest n_contrib, list length)
-    ex = _C.debug_export(P, W, H, num_rendered, geom_b, bin_b, img_b, dev)
-    gx, gy = (W + 15) // 16, (H + 15) // 16
-    ncp = torch.zeros((gy * 16, gx * 16), dtype=torch.int64, device=dev)
-    ncp[:H, :W] = ex["n_contrib"].to(torch.int64)
-    tmax = ncp.view(gy, 16, gx, 16).amax(dim=(1, 3)).reshape(-1)
-    rg = ex["ranges"].to(torch.int64)
-    walked = int(torch.minimum(tmax, rg[:, 1] - rg[:, 0]).sum())
-    del ex, geom_b, bin_b, img_b
+    if args.full:
+        # workload counters (one extra forward, untimed)
+        e = torch.Tensor([])
+        num_rendered, _, radii, geom_b, bin_b, img_b = _C.rasterize_gaussians(
+            settings.bg, d.means3D, e, d.opacities, d.scales, d.rotations, 1.0, e, settings.viewmatrix,
+            settings.projmatrix, settings.tanfovx, settings.tanfovy, H, W, d.shs, deg, settings.campos, False, False)
+        visible = int((radii > 0).sum())
+        tiles = ((W + 15) // 16) * ((H + 15) // 16)
+        # instances the render walks reach: per tile min(largest n_contrib, list length)
+        ex = _C.debug_export(P, W, H, num_rendered, geom_b, bin_b, img_b, dev)
+        gx, gy = (W + 15) // 16, (H + 15) // 16
+        ncp = torch.zeros((gy * 16, gx * 16), dtype=torch.int64, device=dev)
+        ncp[:H, :W] = ex["n_contrib"].to(torch.int64)
+        tmax = ncp.view(gy, 16, gx, 16).amax(dim=(1, 3)).reshape(-1)
+        rg = ex["ranges"].to(torch.int64)
+        walked = int(torch.minimum(tmax, rg[:, 1] - rg[:, 0]).sum())
+        del ex, geom_b, bin_b, img_b
 
     if args.profile_pass_only:
         # only the kernel-duration pass below (its one-stream step), nothing else on the device
@@ -324,9 +346,11 @@ def main():
     torch.cuda.reset_peak_memory_stats(dev)
     # `regions` timed regions of exactly K steps each, every one bracketed by a barrier and a device
     # sync (max over ranks); `value` is the median region (host-bound configurations such as C2 vary
-    # from region to region with the box's host load; every region is reported)
+    # from region to region with the box's host load; every region is reported).  A plain run times
+    # one region: exactly --steps steps; --full five
+    n_regions = args.regions if args.regions is not None else (5 if args.full else 1)
     region_s = []
-    for reg in range(max(1, args.regions)):
+    for reg in range(max(1, n_regions)):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -351,6 +375,59 @@ def main():
         region_s.append(el)
     elapsed = sorted(region_s)[len(region_s) // 2]
     peak_hbm = torch.cuda.max_memory_allocated(dev)
+
+    ms_per_step = 1e3 * elapsed / args.steps
+    # whole-job views (= reference train iterations) per second: weak scaling (C1-C3, C5) counts
+    # every rank's views; a C4 step is the 8-view batch
+    views_per_step = n_views or world * len(my_views)
+    value = views_per_step * args.steps / elapsed
+    ms_per_view = ms_per_step / len(my_views)
+    headline = {
+        "metric": "train iters/sec (fwd+bwd) + render Mpix/s @1080p, 1M Gaussians SH=3",
+        "value": round(value, 2),
+        "unit": "iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if (n_views and args.c4_views_per_rank <= 0) else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded; SURVEY.md §8d distribution)",
+        "config": {"workload": wl["desc"], "gaussians": P, "sh_degree": deg, "width": W, "height": H,
+                   "views_per_rank_per_step": len(my_views), "views_per_step": views_per_step,
+                   "render_exp2": "exact-polynomial" if os.environ.get("GSRAST_EXACT_EXP", "0") not in ("", "0")
+                   else "hardware v_exp_f32",
+                   "parallelism": f"view-parallel dp{world}" +
+                   (f" + {'RCCL' if backend == 'nccl' else backend} all-reduce of 59 f32/Gaussian in "
+                    f"{bucket.chunks} row chunks overlapped with the per-Gaussian pass" if world > 1 else ""),
+                   "backend": backend if world > 1 else None},
+    }
+
+    # what the last timed step computed, before anything else runs on the device
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last_views, params)
+    last_views = None  # the steps below keep no outputs
+
+    if not args.full:
+        # the plain run ends here: set-up, warm-up, the timed steps, the headline
+        headline.update({
+            "ms_per_view": round(ms_per_view, 4),
+            "hbm": {"peak_allocated_GB": round(peak_hbm / 1e9, 3)},
+            "regions_iters_s": [round(views_per_step * args.steps / r_, 2) for r_ in region_s],
+            "streams": len(streams),
+            "fused_front": fused_front,
+            **({"step_ms_deciles": _step_deciles(evs, args.steps)} if args.step_events else {}),
+            **({"dumped_outputs": dumped} if dumped else {}),
+            "full": False,
+        })
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # sustained rate: keep stepping for ~--sustain-s (a longer region than the K timed steps,
     # which last only tens of ms; the same step, reported beside `value`, not instead of it)
@@ -461,12 +538,6 @@ def main():
         graphs = graph_bench(bucket, rasts, params, dpix, streams, fused_front, step, args.steps,
                              args.single_view_steps, len(my_views))
 
-    ms_per_step = 1e3 * elapsed / args.steps
-    # whole-job views (= reference train iterations) per second: weak scaling (C1-C3, C5) counts
-    # every rank's views; a C4 step is the 8-view batch
-    views_per_step = n_views or world * len(my_views)
-    value = views_per_step * args.steps / elapsed
-
     # per-kernel breakdown + roofline of the dominant kernel
     k_local = len(my_views)
     acc_frac = (k_local - 1) / k_local  # preprocess_bwd launches that add into the bucket
@@ -517,7 +588,6 @@ def main():
     # bytes per launch times its launches per step, over the step's views
     step_bytes = sum((kb(k) or 0)
                      * v["launches_per_step"] for k, v in kernels.items()) / k_local
-    ms_per_view = ms_per_step / k_local
     step_roofline = dict(algo_bytes_per_view=int(step_bytes), ms_per_view=round(ms_per_view, 4),
                          achieved=round(step_bytes / (ms_per_view * 1e-3) / 1e9, 1), peak=HBM_PEAK_GBS, unit="GB/s",
                          frac=round(step_bytes / (ms_per_view * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
@@ -549,32 +619,9 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(sc, cam, deg, W, H, dpix.cpu(), args.cpu_threads, args.cpu_runs)
 
-    step_deciles = None
-    if args.step_events:
-        st_ms = [evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps)]
-        nd = max(1, args.steps // 10)
-        step_deciles = [round(sum(st_ms[j:j + nd]) / len(st_ms[j:j + nd]), 4) for j in range(0, args.steps, nd)]
+    step_deciles = _step_deciles(evs, args.steps) if args.step_events else None
     out = {
-        "metric": "train iters/sec (fwd+bwd) + render Mpix/s @1080p, 1M Gaussians SH=3",
-        "value": round(value, 2),
-        "unit": "iters/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "strong" if (n_views and args.c4_views_per_rank <= 0) else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (seeded; SURVEY.md §8d distribution)",
-        "config": {"workload": wl["desc"], "gaussians": P, "sh_degree": deg, "width": W, "height": H,
-                   "views_per_rank_per_step": len(my_views), "views_per_step": views_per_step,
-                   "render_exp2": "exact-polynomial" if os.environ.get("GSRAST_EXACT_EXP", "0") not in ("", "0")
-                   else "hardware v_exp_f32",
-                   "parallelism": f"view-parallel dp{world}" +
-                   (f" + {'RCCL' if backend == 'nccl' else backend} all-reduce of 59 f32/Gaussian in "
-                    f"{bucket.chunks} row chunks overlapped with the per-Gaussian pass" if world > 1 else ""),
-                   "backend": backend if world > 1 else None},
+        **headline,
         "render_mpix_s": round(W * H / t_render / 1e6, 1),
         "render_ms": round(1e3 * t_render, 4),
         "render_batched": render_batched,
@@ -606,12 +653,71 @@ def main():
         "view_parallel_train": vp_train,
         "init_knn": knn,
         **({"step_ms_deciles": step_deciles} if step_deciles else {}),
+        **({"dumped_outputs": dumped} if dumped else {}),
+        "full": True,
         "cpu_baseline": cpu,
     }
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def _step_deciles(evs, steps):
+    st_ms = [evs[k].elapsed_time(evs[k + 1]) for k in range(steps)]
+    nd = max(1, steps // 10)
+    return [round(sum(st_ms[j:j + nd]) / len(st_ms[j:j + nd]), 4) for j in range(0, steps, nd)]
+
+
+DUMP_BUDGET = 64 * 10**6  # bytes of --dump-outputs, all files together
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, last_views, params):
+    """--dump-outputs: what a caller of the timed step receives from its last run, as float32
+    DIR/<name>.npy (rank 0's views; with N > 1 the gradients are the all-reduced ones):
+      image_view<k>   the K rendered images, [3, n_pix]: the pixels listed in `pixels`
+      radii_view<k>   every view's radii, [n_rows]: the Gaussians listed in `gaussian_rows`
+      grad_<param>    the step's gradients of means3D / shs / opacities / scales / rotations (summed
+                      over the step's views, as they stand in the .grad bucket), [n_rows, ...]
+      pixels, gaussian_rows   the flat pixel indices (y * W + x) and Gaussian indices written, float64
+    Everything is written whole while it fits DUMP_BUDGET bytes; otherwise a quarter of the budget goes
+    to a sorted sample of Gaussian rows and the rest to a sorted sample of pixels, both drawn without
+    replacement from numpy's default_rng(DUMP_SEED): they depend on the workload's sizes only, so two
+    builds run with the same arguments write the same elements.  Returns a summary for the line."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    names = ("means3D", "shs", "opacities", "scales", "rotations")
+    P, K = params[0].shape[0], len(last_views)
+    _, H, W = last_views[0][0].shape
+    row_bytes = 4 * (sum(p[0].numel() for p in params) + K) + 8  # gradients, K radii, the index
+    pix_bytes = 4 * 3 * K + 8  # K RGB values, the index
+    slack = 1 << 16  # .npy headers
+    rng = np.random.default_rng(DUMP_SEED)
+    n_rows, n_pix = P, H * W
+    if P * row_bytes + H * W * pix_bytes + slack > DUMP_BUDGET:
+        n_rows = min(P, DUMP_BUDGET // 4 // row_bytes)
+        n_pix = min(H * W, (DUMP_BUDGET - n_rows * row_bytes - slack) // pix_bytes)
+    rows = np.sort(rng.choice(P, n_rows, replace=False)) if n_rows < P else np.arange(P)
+    pix = np.sort(rng.choice(H * W, n_pix, replace=False)) if n_pix < H * W else np.arange(H * W)
+    dev = params[0].device
+    rows_t, pix_t = torch.from_numpy(rows).to(dev), torch.from_numpy(pix).to(dev)
+    arrays = {"gaussian_rows": rows.astype(np.float64), "pixels": pix.astype(np.float64)}
+    for k in sorted(last_views):
+        img, radii = last_views[k]
+        arrays[f"image_view{k}"] = img.reshape(3, -1)[:, pix_t].float().cpu().numpy()
+        arrays[f"radii_view{k}"] = radii[rows_t].float().cpu().numpy()
+    for name, p in zip(names, params):
+        arrays[f"grad_{name}"] = p.grad.detach()[rows_t].float().cpu().numpy()
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        total += os.path.getsize(path)
+    assert total <= DUMP_BUDGET, f"--dump-outputs wrote {total} bytes"
+    return {"dir": dirname, "files": len(arrays), "bytes": total, "gaussian_rows": [int(n_rows), int(P)],
+            "pixels": [int(n_pix), int(H * W)], "seed": DUMP_SEED}
 
 
 def vp_train_bench(sc, cams, my_views, deg, dev, steps, warmup, world, chunks):

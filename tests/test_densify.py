@@ -2,7 +2,8 @@
 
 Chain of pins:
   * oracle/densify_oracle.py (a restatement of scene/gaussian_model.py:258-403) reproduces the
-    reference's own GaussianModel.densify_and_prune bit for bit on CPU
+    reference's own GaussianModel.densify_and_prune on CPU: bit for bit, except the computed
+    xyz / scaling of split children, held to rtol 1e-6 / atol 1e-6 (HOST_ROUNDED below)
     (tests/golden/densify_golden.npz, made by tests/golden/make_golden.py: same inputs, same
     torch.manual_seed before the call so torch.normal draws the same split samples);
   * on the GPU the HIP path is compared with the oracle on the same inputs and the same CUDA
@@ -20,6 +21,14 @@ from oracle import densify_oracle as DO
 
 G = np.load(__file__.rsplit("/", 1)[0] + "/golden/densify_golden.npz")
 LRS = [1.6e-4, 2.5e-3, 1.25e-4, 5e-2, 5e-3, 1e-3]
+# The split children's xyz and scaling are the only outputs that are computed, not copied, and on
+# CPU torch computes them with the math library's exp / log / sqrt, normal transform and bmm, whose
+# last bit depends on the code path that library picks for the host CPU (the golden file holds
+# the bits of the host it was made on; another host differs in ~3 % of the elements by one ulp).
+# Each passes through at most 8 float32 roundings (2^-24 = 6e-8 relative each, 5e-7 in all), so
+# against the golden file they are held to rtol 1e-6 / atol 1e-6, the bound the GPU comparison
+# uses for xyz; every other tensor, the moments, sizes and steps stay bit-exact.
+HOST_ROUNDED = ("xyz", "scaling")
 
 
 class Model:
@@ -78,7 +87,12 @@ def test_oracle_matches_reference_golden(case):
     assert m._xyz.shape[0] == int(G[f"{case}_out_sizes"][0])
     for grp in m.optimizer.param_groups:
         n = grp["name"]
-        np.testing.assert_array_equal(grp["params"][0].detach().numpy(), G[f"{case}_out_{n}"], err_msg=n)
+        got, want = grp["params"][0].detach().numpy(), G[f"{case}_out_{n}"]
+        if n in HOST_ROUNDED:
+            assert got.shape == want.shape
+            np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6, err_msg=n)
+        else:
+            np.testing.assert_array_equal(got, want, err_msg=n)
         st = m.optimizer.state[grp["params"][0]]
         np.testing.assert_array_equal(st["exp_avg"].numpy(), G[f"{case}_out_{n}_exp_avg"], err_msg=n)
         np.testing.assert_array_equal(st["exp_avg_sq"].numpy(), G[f"{case}_out_{n}_exp_avg_sq"], err_msg=n)

@@ -5,8 +5,8 @@ own Camera, scene/cameras.py:17-57, and GaussianModel getters, scene/gaussian_mo
 with a recording stand-in for the rasterizer).
 
 CPU: gs_scenes' camera builder + raster_settings_for reproduce every GaussianRasterizationSettings
-field bit for bit (tanfov, the W2C^T matrix, full_proj_transform = W2C^T (x) P^T via bmm,
-campos = inverse()[3, :3]).
+field bit for bit (tanfov, the W2C^T matrix, full_proj_transform = W2C^T (x) P^T via bmm), and
+campos = inverse()[3, :3] within 4 ulp (the LAPACK inverse's last bits are the host's).
 GPU: gs_train.render_inputs (the HIP activations) against the getters' tensors, and the recorded
 settings + inputs (including the Python colour / covariance paths, scale_modifier 0.7, a
 non-black background) through GaussianRasterizer against the oracle."""
@@ -57,7 +57,16 @@ def test_raster_settings_bitwise_equal_reference_render(name):
     for k in ("bg", "viewmatrix", "projmatrix", "campos"):
         got = getattr(s, k)
         assert got.dtype == torch.float32, k
-        np.testing.assert_array_equal(got.numpy(), GOLD[f"{name}_{k}"], err_msg=k)
+        want = GOLD[f"{name}_{k}"]
+        if k == "campos":
+            # inverse() is the host's LAPACK (an LU solve of the rigid 4x4 W2C^T): its last bits depend on
+            # the code path the math library picks for the CPU, and the fixture holds those of the host it
+            # was made on.  Held to 4 ulp of the largest coordinate (a 4x4 solve: a few float32 roundings
+            # per element, on matrices with condition number < 100); exact where the camera sits at 0
+            tol = 4 * float(np.spacing(np.abs(want).max()))
+            assert got.shape == want.shape and np.abs(got.numpy() - want).max() <= tol, (k, got, want)
+            continue
+        np.testing.assert_array_equal(got.numpy(), want, err_msg=k)
     mod, deg, pref, dbg = GOLD[f"{name}_scalars"]
     assert (s.scale_modifier, s.sh_degree, s.prefiltered, s.debug) == (mod, int(deg), bool(pref), bool(dbg))
 

@@ -5,7 +5,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
 args=$1; shift
 for v in "$@"; do
-  GSRAST_LIB=$R/gaussian-splatting-skysphere_amd/$v/libgsrast.so timeout -k 10 300 python bench.py --steps ${V_STEPS:-50} --warmup 5 --no-cpu-baseline --no-train-step $args > $OUT/ab_$v.log 2>&1 || { echo "$v failed"; tail $OUT/ab_$v.log; exit 1; }
+  GSRAST_LIB=$R/gaussian-splatting-skysphere_amd/$v/libgsrast.so timeout -k 10 300 python bench.py --full --steps ${V_STEPS:-50} --warmup 5 --no-cpu-baseline --no-train-step $args > $OUT/ab_$v.log 2>&1 || { echo "$v failed"; tail $OUT/ab_$v.log; exit 1; }
   python - "$OUT/ab_$v.log" "$v $args" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])
