@@ -270,6 +270,9 @@ size_t gs_grad_buffer_bytes(long long num_rendered) {
   const size_t R = (size_t)(num_rendered > 0 ? num_rendered : 1);
   return align_up(R * GRAD_REC * sizeof(float));
 }
+size_t gs_grad_buffer_bytes_aux(long long num_rendered, int P) {
+  return grad_layout_aux((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)(P > 0 ? P : 1), nullptr, nullptr);
+}
 
 // Pinned, device-mapped host words: kernels store into them directly (vector stores through the
 // device pointer), so a readback costs no copy launch.
@@ -698,7 +701,7 @@ static int forward_render_impl(int P, const float* background, int W, int H, con
                                const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
                                const int* radii, void* geom_buffer, long long num_rendered, void* binning_buffer,
                                void* image_buffer, float* out_color, bool bounded, int debug, void* stream,
-                               unsigned long long* oseq_out = nullptr) {
+                               unsigned long long* oseq_out = nullptr, const FwdAux& aux = FwdAux()) {
   clear_error(debug);
   if (P <= 0) return 0;
   if (W <= 0 || H <= 0) return set_error("image size must be positive"), 1;
@@ -723,7 +726,7 @@ static int forward_render_impl(int P, const float* background, int W, int H, con
   uint32_t* flags_word = bounded ? (bs ? bs->dev + 4 : nullptr) : order_flags_word(&oseq);
   if (!flags_word) return 1;
   fwd_bin(P, (uint32_t)num_rendered, c, radii, geo, bin, img, st);
-  fwd_render(c, geo, bin, img, out_color, st, flags_word);
+  fwd_render(c, geo, bin, img, out_color, st, flags_word, aux);
   if (!bounded) {
     if (oseq_out) *oseq_out = oseq;
     if (t_failed) release_order_word(oseq);
@@ -831,6 +834,19 @@ int gs_forward_render(int P, const float* background, int W, int H, const float*
                       void* stream) {
   return forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
                              geom_buffer, num_rendered, binning_buffer, image_buffer, out_color, false, debug, stream);
+}
+
+int gs_forward_render_aux(int P, const float* background, int W, int H, const float* viewmatrix,
+                          const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                          const int* radii, void* geom_buffer, long long num_rendered, void* binning_buffer,
+                          void* image_buffer, float* out_color, float* out_invdepth, float* out_alpha, int debug,
+                          void* stream) {
+  FwdAux aux;
+  aux.invdepth = out_invdepth;
+  aux.alpha = out_alpha;
+  return forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                             geom_buffer, num_rendered, binning_buffer, image_buffer, out_color, false, debug, stream,
+                             nullptr, aux);
 }
 
 int gs_forward_render_bounded(int P, const float* background, int W, int H, const float* viewmatrix,
@@ -1010,7 +1026,8 @@ static int backward_impl(int P, int D, int M, const float* background, int W, in
                          const void* image_buffer, const float* dL_dout_color, void* grad_buffer, float* dL_dmeans2D,
                          float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                          float* dL_dscales, float* dL_drotations, unsigned accumulate, void* wait_event, int debug,
-                         void* stream) {
+                         void* stream, const float* dL_dout_invdepth = nullptr,
+                         const float* dL_dout_alpha = nullptr) {
   clear_error(debug);
   (void)opacities;  // the opacity is carried by the forward's splat records
   if (!validate(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
@@ -1034,7 +1051,17 @@ static int backward_impl(int P, int D, int M, const float* background, int W, in
   GaussianArgs g{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier,
                  shs_rest};
   float* gradrec = (float*)grad_buffer;
-  if (num_rendered > 0) bwd_render(P, c, geo, bin, img, dL_dout_color, gradrec, st);
+  // an aux gradient (gs_backward_accumulate_aux): the side arrays behind the records; none: the plain path
+  BwdAux aux;
+  if (dL_dout_invdepth || dL_dout_alpha) {
+    size_t o_rec = 0, o_sum = 0;
+    grad_layout_aux((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)P, &o_rec, &o_sum);
+    aux.d_invdepth = dL_dout_invdepth;
+    aux.d_alpha = dL_dout_alpha;
+    aux.gradrec_aux = (float*)((char*)grad_buffer + o_rec);
+    aux.gsum_aux = (float*)((char*)grad_buffer + o_sum);
+  }
+  if (num_rendered > 0) bwd_render(P, c, geo, bin, img, dL_dout_color, gradrec, st, aux);
   // dL_dcov3D is filled whenever the caller passes it: upstream writes it for scale/rotation
   // inputs too (the covariance gradient the scale / rotation chain starts from)
   GradOut out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
@@ -1042,7 +1069,11 @@ static int backward_impl(int P, int D, int M, const float* background, int W, in
               accumulate};
   // the gradient outputs may be shared with views on other streams: order only this last kernel
   if (wait_event && !check_hip(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0), "hipStreamWaitEvent")) return 1;
-  bwd_preprocess(g, c, geo, bin, img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st);
+  bwd_preprocess(g, c, geo, bin, img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st, aux);
+  if (aux.on() && num_rendered > 0) {
+    // the depth chain's term, added after the kernel that wrote dL_dmeans3D (same stream, behind the wait)
+    bwd_depth_chain(g, c, geo, aux, dL_dmeans3D, st);
+  }
   // the ordering flags of the forwards that have finished, now that this backward's kernels are queued
   if (!t_failed && check_order_flags(false)) return 1;
   return t_failed ? 1 : 0;
@@ -1080,6 +1111,25 @@ int gs_backward_accumulate(int P, int D, int M, const float* background, int W, 
                        num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dmeans2D,
                        dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, accumulate,
                        wait_event, debug, stream);
+}
+
+int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                               const float* shs, const float* shs_rest, const float* colors_precomp,
+                               const float* opacities, const float* scales, float scale_modifier,
+                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                               const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                               const int* radii, const void* geom_buffer, long long num_rendered,
+                               const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                               const float* dL_dout_invdepth, const float* dL_dout_alpha, void* grad_buffer,
+                               float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
+                               float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                               unsigned accumulate, void* wait_event, int debug, void* stream) {
+  (void)radii;
+  return backward_impl(P, D, M, background, W, H, means3D, shs, shs_rest, colors_precomp, opacities, scales,
+                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                       geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer,
+                       dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+                       dL_drotations, accumulate, wait_event, debug, stream, dL_dout_invdepth, dL_dout_alpha);
 }
 
 int gs_backward_accumulate_split(int P, int D, int M, const float* background, int W, int H, const float* means3D,

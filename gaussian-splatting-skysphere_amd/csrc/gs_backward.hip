@@ -63,10 +63,14 @@ __device__ __forceinline__ void load_rec(const float* p, float* v) {
 struct BwdSlot {
   float T, U, d0, d1, d2;
   uint32_t last;
+  float gD;  // AUX: dL/dinvdepth of the pixel (else unused)
 };
 
 // one slot's evaluation + commit for one entry; s[] accumulates the lane's slot terms
-template <bool EXACT>
+// AUX (gs_backward_accumulate_aux): the inverse depth is one more colour channel, of colour 1 / z
+// (br.w) and pixel gradient gD: Cd gains (1 / z) gD and s[9] sums dch gD = dL/d(1 / z).  (Alpha, a
+// channel of colour 0 and background -1, only changes U's start.)
+template <bool EXACT, bool AUX = false>
 __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, const float4 xr, const float4 co,
                                          const float4 br, uint32_t e, float* s) {
   const float bl = br.x;
@@ -84,7 +88,8 @@ __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, c
   if constexpr (EXACT) inv = __builtin_fmaf(inv, __builtin_fmaf(-omA, inv, 1.0f), inv);
   const float Tn = q.T * inv;
   const float dch = ae * Tn;
-  const float Cd = __builtin_fmaf(bl, q.d2, __builtin_fmaf(xr.w, q.d1, xr.z * q.d0));
+  float Cd = __builtin_fmaf(bl, q.d2, __builtin_fmaf(xr.w, q.d1, xr.z * q.d0));
+  if constexpr (AUX) Cd = __builtin_fmaf(br.w, q.gD, Cd);
   const float dLa = __builtin_fmaf(Tn, Cd, -(q.U * inv));
   const float qq = oGm * dLa;  // dL/dG G = o G dL/dalpha (not gated by the 0.99 clamp)
   // moments of q about the entry's reference point r = the splat mean clamped to the tile's pixel
@@ -103,6 +108,7 @@ __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, c
   s[6] = __builtin_fmaf(qx, my, s[6]);
   s[7] = __builtin_fmaf(qy, my, s[7]);
   s[8] = s[8] + qq;
+  if constexpr (AUX) s[9] = __builtin_fmaf(dch, q.gD, s[9]);
   q.T = Tn;
   q.U = __builtin_fmaf(Cd, dch, q.U);
   // the lanes where this slot contributes, from the compares' own lane masks (a ballot of their
@@ -112,7 +118,7 @@ __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, c
   return m;
 }
 
-template <bool EXACT>
+template <bool EXACT, bool AUX = false>
 __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2* __restrict__ ranges,
                                                                     const uint32_t* __restrict__ point_list,
                                                                     const uint32_t* __restrict__ point_gid,
@@ -122,13 +128,15 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
                                                                     const uint32_t* __restrict__ tile_max,
                                                                     const uint32_t* __restrict__ tile_order,
                                                                     const float* __restrict__ dL_dpix,
-                                                                    float* __restrict__ gradrec) {
+                                                                    float* __restrict__ gradrec, BwdAux aux) {
   __shared__ float4 s_xy[64];  // (x, y, r, g)
   __shared__ float4 s_co[64];  // falloff coefficients + opacity (fall_coefs)
   __shared__ float4 s_br[64];  // (b, mean - r: x, y, -), r the moments' reference point (bwd_slot)
   // entry rows of 16 floats (a stride of 20, which puts the flush's 16-B row reads on distinct
   // banks, measured 343 -> 361 us at C3)
-  constexpr int ROW = 16;
+  // (AUX: eight more floats, the partials of s9)
+  constexpr int ROW = AUX ? 24 : 16;
+  constexpr int NS = AUX ? GRAD_REC + 1 : GRAD_REC;  // per-entry sums
   __shared__ __attribute__((aligned(16))) float s_acc[64][ROW];
   GS_BWD_T0();
   const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order ? tile_order[blockIdx.x] : blockIdx.x);
@@ -165,6 +173,12 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
     p[k].d2 = in ? dL_dpix[2 * HW + pix] : 0.0f;
     // U = S + T_final bg . dL/dpix (see k_render_bwd)
     p[k].U = Tf * (c.bg[0] * p[k].d0 + c.bg[1] * p[k].d1 + c.bg[2] * p[k].d2);
+    if constexpr (AUX) {
+      // alpha = 1 - T_final: a channel of background -1
+      const float gA = in && aux.d_alpha ? aux.d_alpha[pix] : 0.0f;
+      p[k].U = p[k].U - Tf * gA;
+      p[k].gD = in && aux.d_invdepth ? aux.d_invdepth[pix] : 0.0f;
+    }
   }
   const float ddelx_dx = (float)(0.5 * c.W), ddely_dy = (float)(0.5 * c.H);
   const float pfx0 = (float)qx0, pfy0 = (float)qy0;
@@ -199,6 +213,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
       r[0] = Rec3{a.x, a.y, a.z};
       r[1] = Rec3{a.w, b.x, b.y};
       r[2] = Rec3{b.z, b.w, d.x};
+      if constexpr (AUX) aux.gradrec_aux[__float_as_uint(d.y)] = d.z;
     }
   };
   for (uint32_t base = 0; base < n_eff; base += 64) {
@@ -212,8 +227,9 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
       s_xy[lane] = make_float4(pa.x, pa.y, pb.z, pb.w);
       s_co[lane] = fall_coefs_m<EXACT>(pa.z, pa.w, pb.x, pb.y);
       const float x0 = (float)(tx * GS_TILE), y0 = (float)(ty * GS_TILE);
+      // (AUX: 1 / z, the division of the forward's staging)
       s_br[lane] = make_float4(pd.x, pa.x - fminf(fmaxf(pa.x, x0), x0 + 15.0f),
-                               pa.y - fminf(fmaxf(pa.y, y0), y0 + 15.0f), 0.0f);
+                               pa.y - fminf(fmaxf(pa.y, y0), y0 + 15.0f), AUX ? 1.0f / pd.y : 0.0f);
       qmask = quadrant_mask(pa.x, pa.y, pa.z, pa.w, pb.x, pd.z, tx, ty);
     }
     // issue the next batch's splat loads, the ids after it and (ids by slot) the slots after those
@@ -247,9 +263,9 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
       const uint32_t e = n_eff - 1 - (base + j);
       // -0 (the additive identity of IEEE addition): the first contributing slot's FMAs / adds into
       // it fold to plain products / moves (with +0 they cannot: x + 0 differs from x for x = -0)
-      float s[GRAD_REC];
+      float s[NS];
 #pragma unroll
-      for (int t = 0; t < GRAD_REC; t++) s[t] = -0.0f;
+      for (int t = 0; t < NS; t++) s[t] = -0.0f;
 #ifdef GS_TIMING
       t_walked++;
       t_slots += ((M[0] >> j) & 1ull) + ((M[1] >> j) & 1ull) + ((M[2] >> j) & 1ull) + ((M[3] >> j) & 1ull);
@@ -258,18 +274,25 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
 #pragma unroll
       for (int k = 0; k < 4; k++)
         if ((M[k] >> j) & 1ull)
-          con |= bwd_slot<EXACT>(p[k], pfx0 + (float)(8 * (k & 1)), pfy0 + (float)(8 * (k >> 1)), xr, co, br, e, s);
+          con |= bwd_slot<EXACT, AUX>(p[k], pfx0 + (float)(8 * (k & 1)), pfy0 + (float)(8 * (k >> 1)), xr, co, br, e, s);
       if (con != 0) {
         wrote |= 1ull << j;
         float d, d8;
-        wave_sum9_halfrows(s, hi8, d, d8);
-        asm volatile("" ::"v"(d), "v"(d8));
+        [[maybe_unused]] float d9;
+        if constexpr (AUX) {
+          wave_sum10_halfrows(s, hi8, d, d8, d9);
+          asm volatile("" ::"v"(d), "v"(d8), "v"(d9));
+        } else {
+          wave_sum9_halfrows(s, hi8, d, d8);
+          asm volatile("" ::"v"(d), "v"(d8));
+        }
         if ((lane & 7) == 0) {
           uint32_t eo = j * ROW;
           asm volatile("" : "+s"(eo));
           lds_float* acc = acc_lane + eo;
           acc[0] = d;
           acc[8] = d8;
+          if constexpr (AUX) acc[16] = d9;
         }
       }
     }
@@ -277,7 +300,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
     // flush: lane t maps the sums of its entry into the record (zeros for an entry no pixel took),
     // written back into its LDS row with the slot; stored by the next batch (or after the loop)
     if (mine) {
-      float S[GRAD_REC];
+      float S[NS];
       if ((wrote >> lane) & 1ull) {
         const float4 a0 = *reinterpret_cast<const float4*>(&s_acc[lane][0]);
         const float4 a1 = *reinterpret_cast<const float4*>(&s_acc[lane][4]);
@@ -285,9 +308,14 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
         const float4 a3 = *reinterpret_cast<const float4*>(&s_acc[lane][12]);
         S[0] = a0.x, S[1] = a0.y, S[2] = a0.z, S[3] = a0.w, S[4] = a1.x, S[5] = a1.y, S[6] = a1.z, S[7] = a1.w;
         S[8] = ((a2.x + a2.y) + (a2.z + a2.w)) + ((a3.x + a3.y) + (a3.z + a3.w));
+        if constexpr (AUX) {  // the eight partials of s9, in the fixed order of s8's
+          const float4 a4 = *reinterpret_cast<const float4*>(&s_acc[lane][16]);
+          const float4 a5 = *reinterpret_cast<const float4*>(&s_acc[lane][20]);
+          S[9] = ((a4.x + a4.y) + (a4.z + a4.w)) + ((a5.x + a5.y) + (a5.z + a5.w));
+        }
       } else {
 #pragma unroll
-        for (int t = 0; t < GRAD_REC; t++) S[t] = 0.0f;
+        for (int t = 0; t < NS; t++) S[t] = 0.0f;
       }
       // S3..S7 are the moments of q about the reference point r; with R = mean - r (dx = u + R):
       // sum q dx = S3 + R.x S8, sum q dx^2 = S5 + 2 R.x S3 + R.x^2 S8, ... in fp64, one rounding to
@@ -307,7 +335,10 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
       row[0] = make_float4(S[0], S[1], S[2], -ddelx_dx * (ccx * m1x + ccy * m1y));
       row[1] = make_float4(-ddely_dy * (ccz * m1y + ccy * m1x), -0.5f * m2xx, -0.5f * m2xy, -0.5f * m2yy);
       // S8 = o sum G dL/dalpha (a contributor has o >= 1/255)
-      row[2] = make_float4(S[8] != 0.0f ? S[8] / cop : 0.0f, __uint_as_float(slot), 0.0f, 0.0f);
+      // (AUX: word 10 = dL/d(1 / z) of the instance, stored to gradrec_aux[slot])
+      float s9 = 0.0f;
+      if constexpr (AUX) s9 = S[9];
+      row[2] = make_float4(S[8] != 0.0f ? S[8] / cop : 0.0f, __uint_as_float(slot), s9, 0.0f);
     }
     rec_lanes = cnt;
     __builtin_amdgcn_wave_barrier();  // the next batch overwrites the staged entries
@@ -372,19 +403,27 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_tile_order(const uint32_t* __
 }
 
 void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
-                const float* dL_dpix, float* gradrec, hipStream_t st) {
+                const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux) {
   const int tiles = c.gx * c.gy;
   uint32_t* order = img.tile_order;
   const uint32_t slots = (uint32_t)tiles;
   GS_LAUNCH("tile_order", k_tile_order, dim3((slots + ORDER_THREADS - 1) / ORDER_THREADS), dim3(ORDER_THREADS), 0, st,
             img.len_hist, img.tile_brank, (uint32_t)c.gx, (uint32_t)c.gy, order, img.tile_max, img.ranges,
             bin.point_list, img.tile_cut, img.cut_max);
-  if (exact_exp())
-    GS_LAUNCH("render_bwd", k_render_bwd_tw<true>, dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list,
-              bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, gradrec);
-  else
-    GS_LAUNCH("render_bwd", k_render_bwd_tw<false>, dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list,
-              bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, gradrec);
+#define GS_BWDTW(NAME, EXACT, AUX)                                                                           \
+  GS_LAUNCH(NAME, (k_render_bwd_tw<EXACT, AUX>), dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list, \
+            bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, gradrec, aux)
+  if (aux.on()) {  // an aux gradient: the AUX walk (gs_backward_accumulate_aux)
+    if (exact_exp())
+      GS_BWDTW("render_bwd_aux", true, true);
+    else
+      GS_BWDTW("render_bwd_aux", false, true);
+  } else if (exact_exp()) {
+    GS_BWDTW("render_bwd", true, false);
+  } else {
+    GS_BWDTW("render_bwd", false, false);
+  }
+#undef GS_BWDTW
 }
 
 // ------------------------------------------------------------------------------------------
@@ -401,14 +440,18 @@ void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& 
 constexpr int SUMREC_WAVES = 4;  // (2 or 8 measured within 2 us at C3)
 // one step of the segmented wave scan: v += (shifted v) when the shifted lane has the same owner
 // (owners are carried +1 so a lane without a source (0) never matches)
-template <int CTRL, int ROW_MASK>
+template <int CTRL, int ROW_MASK, int NC = GRAD_REC>
 __device__ __forceinline__ void seg_scan_step(float* v, uint32_t own1) {
   const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own1, CTRL, ROW_MASK, 0xF, false);
   const float f = o == own1 ? 1.0f : 0.0f;
 #pragma unroll
-  for (int c = 0; c < GRAD_REC; c++) v[c] = __builtin_fmaf(dpp_f<CTRL, ROW_MASK>(v[c]), f, v[c]);
+  for (int c = 0; c < NC; c++) v[c] = __builtin_fmaf(dpp_f<CTRL, ROW_MASK>(v[c]), f, v[c]);
 }
 
+// AUX (the aux backward): a tenth column, the instance's dL/d(1 / z) from the side array
+// gradrec_aux[slot], summed by the same rule into gsum_aux[gid]; the 9-wide instantiation is the
+// plain backward's.
+template <bool AUX = false>
 __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_t* __restrict__ counters,
                                                                    const uint32_t* __restrict__ offsets,
                                                                    const uint32_t* __restrict__ sorted_gid,
@@ -416,16 +459,21 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
                                                                    const uint32_t* __restrict__ tile_cut,
                                                                    const uint32_t* __restrict__ cut_max,
                                                                    const float* __restrict__ gradrec,
-                                                                   float* __restrict__ gsum, uint32_t P) {
-  __shared__ double s_acc[SUMREC_WAVES][64][GRAD_REC];
+                                                                   float* __restrict__ gsum, uint32_t P,
+                                                                   const float* __restrict__ gradrec_aux,
+                                                                   float* __restrict__ gsum_aux) {
+  constexpr int NC = AUX ? GRAD_REC + 1 : GRAD_REC;
+  __shared__ double s_acc[SUMREC_WAVES][64][NC];
   __shared__ unsigned long long s_mark[SUMREC_WAVES];
   const uint32_t V = counters[CNT_V], I = counters[CNT_I];
   const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t r0 = (blockIdx.x * SUMREC_WAVES + wid) * 64;
   if (counters[CNT_ERR] & ERR_INVALID) {
     // the forward's instance list is invalid (reported by the host): no valid records, zero sums
-    if (r0 + lane < P)
+    if (r0 + lane < P) {
       for (int c = 0; c < GRAD_REC; c++) gsum[(size_t)(r0 + lane) * GRAD_REC + c] = 0.0f;
+      if constexpr (AUX) gsum_aux[r0 + lane] = 0.0f;
+    }
     return;
   }
   if (r0 >= V) return;  // wave-uniform; the kernel has no workgroup barrier
@@ -435,32 +483,36 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
   // the wave's records end at its last owner's end or at the largest tile cut, whichever is first
   const uint32_t S1 = min((r0 + 64 < V) ? offsets[r0 + 64] : I, *cut_max);
 #pragma unroll
-  for (int c = 0; c < GRAD_REC; c++) s_acc[wid][lane][c] = 0.0;
+  for (int c = 0; c < NC; c++) s_acc[wid][lane][c] = 0.0;
   const unsigned long long le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
   uint32_t jbase = 0xFFFFFFFFu;  // (number of owners starting before `base`) - 1
   // records of the next chunk are loaded one chunk ahead (their HBM latency overlaps this chunk)
-  float vn[GRAD_REC];
+  float vn[NC];
   unsigned long long hn;  // lanes of the next chunk that hold a record
   {
     const uint32_t kk = S0 + lane;
 #pragma unroll
-    for (int c = 0; c < GRAD_REC; c++) vn[c] = 0.0f;
+    for (int c = 0; c < NC; c++) vn[c] = 0.0f;
     const bool h = kk < S1 && kk < tile_cut[slot_tile[kk]];
     if (h) load_rec(gradrec + (size_t)kk * GRAD_REC, vn);
+    if constexpr (AUX)
+      if (h) vn[GRAD_REC] = gradrec_aux[kk];
     hn = __ballot(h);
   }
   for (uint32_t base = S0; base < S1; base += 64) {
-    float v[GRAD_REC];
+    float v[NC];
 #pragma unroll
-    for (int c = 0; c < GRAD_REC; c++) v[c] = vn[c];
+    for (int c = 0; c < NC; c++) v[c] = vn[c];
     const unsigned long long hc = hn;
     if (base + 64 < S1) {
       // records past their tile's cut were never written: zeros (no load)
       const uint32_t kn = base + 64 + lane;
 #pragma unroll
-      for (int c = 0; c < GRAD_REC; c++) vn[c] = 0.0f;
+      for (int c = 0; c < NC; c++) vn[c] = 0.0f;
       const bool h = kn < S1 && kn < tile_cut[slot_tile[kn]];
       if (h) load_rec(gradrec + (size_t)kn * GRAD_REC, vn);
+      if constexpr (AUX)
+        if (h) vn[GRAD_REC] = gradrec_aux[kn];
       hn = __ballot(h);
     }
     if (hc == 0) {
@@ -480,18 +532,18 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
     const uint32_t k = base + lane;
     const bool valid = k < S1;
 #pragma unroll
-    for (int c = 0; c < GRAD_REC; c++) v[c] = valid ? v[c] : 0.0f;
+    for (int c = 0; c < NC; c++) v[c] = valid ? v[c] : 0.0f;
     const uint32_t own1 = valid ? own + 1 : 0;
-    seg_scan_step<0x111, 0xF>(v, own1);  // row_shr:1
-    seg_scan_step<0x112, 0xF>(v, own1);  // row_shr:2
-    seg_scan_step<0x114, 0xF>(v, own1);  // row_shr:4
-    seg_scan_step<0x118, 0xF>(v, own1);  // row_shr:8
-    seg_scan_step<0x142, 0xA>(v, own1);  // row_bcast:15 -> rows 1, 3
-    seg_scan_step<0x143, 0xC>(v, own1);  // row_bcast:31 -> rows 2, 3
+    seg_scan_step<0x111, 0xF, NC>(v, own1);  // row_shr:1
+    seg_scan_step<0x112, 0xF, NC>(v, own1);  // row_shr:2
+    seg_scan_step<0x114, 0xF, NC>(v, own1);  // row_shr:4
+    seg_scan_step<0x118, 0xF, NC>(v, own1);  // row_shr:8
+    seg_scan_step<0x142, 0xA, NC>(v, own1);  // row_bcast:15 -> rows 1, 3
+    seg_scan_step<0x143, 0xC, NC>(v, own1);  // row_bcast:31 -> rows 2, 3
     const uint32_t next1 = (uint32_t)__shfl_down((int)own1, 1, 64);
     if (valid && (lane == 63 || next1 != own1)) {
 #pragma unroll
-      for (int c = 0; c < GRAD_REC; c++) atomicAdd(&s_acc[wid][own][c], (double)v[c]);  // ds_add_f64: one lane per owner, fixed order
+      for (int c = 0; c < NC; c++) atomicAdd(&s_acc[wid][own][c], (double)v[c]);  // ds_add_f64: one lane per owner, fixed order
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -499,14 +551,46 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
     const size_t gid = sorted_gid[r0 + lane];
 #pragma unroll
     for (int c = 0; c < GRAD_REC; c++) gsum[gid * GRAD_REC + c] = (float)s_acc[wid][lane][c];
+    if constexpr (AUX) gsum_aux[gid] = (float)s_acc[wid][lane][GRAD_REC];
   }
 }
 
+// The depth chain of the aux backward: 1 / z_i entered invdepth with z_i = the view depth of the
+// mean (row-vector convention of xf43: z = m . (view[2], view[6], view[10]) + view[14]), so
+// dL/dz = -s9 / z^2 and dL/dmeans3D[i] += dL/dz (view[2], view[6], view[10]): an fp32 old + new after
+// the kernel that wrote the row.  Gaussians without instances have no sum (and no term).
+__global__ __launch_bounds__(256) void k_depth_chain_aux(int P, const uint32_t* __restrict__ tiles,
+                                                         const float4* __restrict__ splat,
+                                                         const float* __restrict__ gsum_aux,
+                                                         const float* __restrict__ view,
+                                                         float* __restrict__ dmean3D) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= P || tiles[i] == 0) return;
+  const float z = splat[3 * i + 2].y;
+  const float dz = -gsum_aux[i] / (z * z);
+  dmean3D[3 * i + 0] = dmean3D[3 * i + 0] + dz * view[2];
+  dmean3D[3 * i + 1] = dmean3D[3 * i + 1] + dz * view[6];
+  dmean3D[3 * i + 2] = dmean3D[3 * i + 2] + dz * view[10];
+}
+
+void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BwdAux& aux,
+                     float* dmean3D, hipStream_t st) {
+  if (g.P <= 0) return;
+  GS_LAUNCH("depth_chain_aux", k_depth_chain_aux, dim3((g.P + 255) / 256), dim3(256), 0, st, g.P, geo.tiles,
+            geo.splat, aux.gsum_aux, c.view, dmean3D);
+}
+
 static void launch_sum_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
-                               float* gradrec, uint32_t R, hipStream_t st) {
-  GS_LAUNCH("sum_records", k_sum_records, dim3((g.P + 64 * SUMREC_WAVES - 1) / (64 * SUMREC_WAVES)),
-            dim3(64 * SUMREC_WAVES), 0, st, geo.counters, geo.offsets, geo.sorted_gid, bin.slot_tile, img.tile_cut,
-            img.cut_max, gradrec, geo.gsum, (uint32_t)g.P);
+                               float* gradrec, uint32_t R, hipStream_t st, const BwdAux& aux = BwdAux()) {
+  const dim3 grid((g.P + 64 * SUMREC_WAVES - 1) / (64 * SUMREC_WAVES)), block(64 * SUMREC_WAVES);
+  if (aux.on())  // the aux backward: the tenth column from / to its side arrays
+    GS_LAUNCH("sum_records_aux", k_sum_records<true>, grid, block, 0, st, geo.counters, geo.offsets, geo.sorted_gid,
+              bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P, aux.gradrec_aux,
+              aux.gsum_aux);
+  else
+    GS_LAUNCH("sum_records", k_sum_records<false>, grid, block, 0, st, geo.counters, geo.offsets, geo.sorted_gid,
+              bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P, (const float*)nullptr,
+              (float*)nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1433,9 +1517,9 @@ void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin,
 
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
-                    bool have_records, const GradOut& out, hipStream_t st) {
+                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux) {
   if (g.P <= 0) return;
-  if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st);
+  if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st, aux);
   dim3 grid((g.P + 255) / 256), block(256);
   const bool sh = g.colors == nullptr && g.shs != nullptr && out.dsh != nullptr;
   if (!sh) {

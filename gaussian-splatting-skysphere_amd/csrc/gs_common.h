@@ -506,6 +506,26 @@ __device__ __forceinline__ void wave_sum9_halfrows(const float* s, bool hi, floa
   d8 = v[1];
 }
 
+// The aux backward's ten sums: wave_sum9_halfrows plus s[9], which is reduced like s[8] (d9: its
+// sum over the lane's 8-lane group of the swapped layout; the eight group values add up to the
+// total).  Fixed order, as there.
+__device__ __forceinline__ void wave_sum10_halfrows(const float* s, bool hi, float& d, float& d8, float& d9) {
+  const float c0 = swap32_add(s[0], s[2]), c1 = swap32_add(s[1], s[3]);
+  const float c2 = swap32_add(s[4], s[6]), c3 = swap32_add(s[5], s[7]);
+  const float a = swap16_add(c0, c1), b = swap16_add(c2, c3);
+  const float keep = hi ? b : a, send = hi ? a : b;
+  float v[3] = {keep + dpp_f<0x128>(send), s[8], s[9]};  // row_ror:8
+#pragma unroll
+  for (int k = 0; k < 3; k++) v[k] = v[k] + dpp_f<0xB1>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) v[k] = v[k] + dpp_f<0x4E>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) v[k] = v[k] + dpp_f<0x141>(v[k]);
+  d = v[0];
+  d8 = v[1];
+  d9 = v[2];
+}
+
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {

@@ -766,7 +766,7 @@ void fwd_bin_views(int views, int P, uint32_t I, const CameraArgs& c, const Geom
 // ------------------------------------------------------------------------------------------
 // Entries are staged as three 16-B LDS records at one byte offset o (o, o + 16 NB, o + 32 NB for
 // a batch of NB entries):
-//   (x, y, r, g) | falloff coefficients + opacity | (b, bits(entry index + 1), -, -)
+//   (x, y, r, g) | falloff coefficients + opacity | (b, bits(entry index + 1), AUX: 1 / z, -)
 // and each quadrant wave's dense list holds the offsets (u32), read FWD_ILP = 4 at a time with one
 // 16-B LDS read: a list entry costs no address arithmetic, no unpacking and no dependent list read.
 // (8 entries per trip: 60 -> 74 VGPRs, 8 -> 6 waves per SIMD, render_fwd 174 -> 189 us)
@@ -775,6 +775,7 @@ static_assert(FWD_ILP % 4 == 0, "list groups are read 16 B at a time");
 
 struct FwdPix {
   float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+  float D = 0.0f;  // AUX: expected inverse depth, one more colour channel of colour 1 / z (else unused)
   uint32_t last = 0;
   uint64_t done;  // lane mask (wave-uniform): pixels that stopped or lie outside the image
 };
@@ -782,7 +783,9 @@ struct FwdPix {
 // Walk one quadrant wave's list of qcnt staged entries for the lane's pixel.  The list is padded
 // with 2 FWD_ILP offsets of a staged dummy entry of opacity 0 (alpha 0 at every pixel), so the walk
 // needs no per-entry end-of-list test (175.8 -> 172.6 us at C3).
-template <bool EXACT, int NB>
+// AUX (the aux outputs, gs_forward_render_aux): the entry's 1 / z rides in word 2 of its third
+// record and is composited into px.D in the form and order of a colour channel.
+template <bool EXACT, int NB, bool AUX = false>
 __device__ __forceinline__ void fwd_walk(const char* ent, const uint32_t* qlist, uint32_t qcnt, float pfx, float pfy,
                                          FwdPix& px) {
   // FWD_ILP entries per trip: their power / exp / alpha chains are independent (ILP); the
@@ -810,8 +813,11 @@ __device__ __forceinline__ void fwd_walk(const char* ent, const uint32_t* qlist,
 #pragma unroll
     for (int u = 0; u < FWD_ILP; u++) {
       const float4 xr = *reinterpret_cast<const float4*>(ent + o[u]);
-      const float2 bl = *reinterpret_cast<const float2*>(ent + o[u] + 32 * NB);
+      using Rec2 = typename std::conditional<AUX, float4, float2>::type;
+      const Rec2 bl = *reinterpret_cast<const Rec2*>(ent + o[u] + 32 * NB);
       const float rr = xr.z, rg = xr.w, rb = bl.x;
+      float rd = 0.0f;
+      if constexpr (AUX) rd = bl.z;
       // branch-free compositing (selects instead of divergent ifs); the per-entry decisions are
       // lane masks combined on the scalar unit (ballot / inverse ballot), so the VALU does the
       // two threshold compares and the selects only.
@@ -830,6 +836,7 @@ __device__ __forceinline__ void fwd_walk(const char* ent, const uint32_t* qlist,
         px.C0 = cu ? px.C0 + rr * al[u] * px.T : px.C0;
         px.C1 = cu ? px.C1 + rg * al[u] * px.T : px.C1;
         px.C2 = cu ? px.C2 + rb * al[u] * px.T : px.C2;
+        if constexpr (AUX) px.D = cu ? px.D + rd * al[u] * px.T : px.D;
         px.T = cu ? tT : px.T;
         px.last = cu ? __float_as_uint(bl.y) : px.last;
       } else {
@@ -844,6 +851,7 @@ __device__ __forceinline__ void fwd_walk(const char* ent, const uint32_t* qlist,
         px.C0 = __builtin_fmaf(rr, wgt, px.C0);
         px.C1 = __builtin_fmaf(rg, wgt, px.C1);
         px.C2 = __builtin_fmaf(rb, wgt, px.C2);
+        if constexpr (AUX) px.D = __builtin_fmaf(rd, wgt, px.D);
         px.T = cu ? tT : px.T;
         px.last = cu ? __float_as_uint(bl.y) : px.last;
       }
@@ -889,6 +897,16 @@ __device__ __forceinline__ void fwd_store(const CameraArgs& c, const QuadPix& q,
     out[2 * HW + pix] = px.C2 + px.T * c.bg[2];
   }
 }
+// the aux outputs of the pixel: no background term; alpha is 1 - final_T as stored (0 for a pixel
+// with no contributor: T is still 1)
+__device__ __forceinline__ void fwd_store_aux(const CameraArgs& c, const QuadPix& q, bool inside, const FwdPix& px,
+                                              float* __restrict__ out_invdepth, float* __restrict__ out_alpha) {
+  if (inside) {
+    const size_t pix = (size_t)q.py * c.W + q.px;
+    if (out_invdepth) out_invdepth[pix] = px.D;
+    if (out_alpha) out_alpha[pix] = 1.0f - px.T;
+  }
+}
 
 // One wave per (tile, quadrant), no workgroup barriers: each wave stages the tile's entries 64 at
 // a time, culls them to its own quadrant and walks them, and finishes as soon as its 64 pixels
@@ -901,13 +919,13 @@ __device__ __forceinline__ void fwd_store(const CameraArgs& c, const QuadPix& q,
 constexpr int FWDQ_NB = 64;  // entries staged per round (one per lane)
 // record stride of the staged batch: one more than the batch for the padding's dummy entry
 constexpr int FWDQ_NBS = FWDQ_NB + 1;
-template <bool EXACT>
+template <bool EXACT, bool AUX = false>
 __global__ __launch_bounds__(64) void k_render_fwd_q(CameraArgs c, const uint2* __restrict__ ranges,
                                                      const uint32_t* __restrict__ point_list,
                                                      const uint32_t* __restrict__ point_gid,
                                                      const float4* __restrict__ splat, float* __restrict__ out,
                                                      ImgPtrs img, const uint32_t* __restrict__ err,
-                                                     uint32_t* __restrict__ err_host) {
+                                                     uint32_t* __restrict__ err_host, FwdAux aux) {
   __shared__ float4 s_ent[3 * FWDQ_NBS];
   __shared__ __attribute__((aligned(16))) uint32_t s_qlist[FWDQ_NB + 2 * FWD_ILP];
   if (threadIdx.x < 3)  // the dummy entry: position 0, opacity 0 (never contributes; fast: log2 0 = -inf)
@@ -942,7 +960,9 @@ __global__ __launch_bounds__(64) void k_render_fwd_q(CameraArgs c, const uint2* 
       const float4 a = splat[3 * gid], bb = splat[3 * gid + 1], d = splat[3 * gid + 2];
       s_ent[lane] = make_float4(a.x, a.y, bb.z, bb.w);
       s_ent[FWDQ_NBS + lane] = fall_coefs_m<EXACT>(a.z, a.w, bb.x, bb.y);
-      s_ent[2 * FWDQ_NBS + lane] = make_float4(d.x, __uint_as_float(base + lane + 1), 0.0f, 0.0f);
+      // (AUX: one correctly rounded division per staged entry; z > 0.2)
+      s_ent[2 * FWDQ_NBS + lane] =
+          make_float4(d.x, __uint_as_float(base + lane + 1), AUX ? 1.0f / d.y : 0.0f, 0.0f);
       meets = d.z >= 0.0f && ellipse_meets_rect(a.x, a.y, a.z, a.w, bb.x, d.z, qx, qx + 7.0f, qy, qy + 7.0f);
     }
     const uint64_t m = __ballot(meets);
@@ -956,10 +976,11 @@ __global__ __launch_bounds__(64) void k_render_fwd_q(CameraArgs c, const uint2* 
     t_batches++;
     t_walked += qcnt;
 #endif
-    fwd_walk<EXACT, FWDQ_NBS>(ent, s_qlist, qcnt, (float)q.px, (float)q.py, px);
+    fwd_walk<EXACT, FWDQ_NBS, AUX>(ent, s_qlist, qcnt, (float)q.px, (float)q.py, px);
     __builtin_amdgcn_wave_barrier();  // the next round overwrites the staged entries
   }
   fwd_store(c, q, inside, px, out, img.final_T, img.n_contrib);
+  if constexpr (AUX) fwd_store_aux(c, q, inside, px, aux.invdepth, aux.alpha);
   const uint32_t wmax = wave_max_u32(px.last);
   if (lane == 0) {
     img.tile_max[4 * tile + wid] = wmax;
@@ -971,15 +992,23 @@ __global__ __launch_bounds__(64) void k_render_fwd_q(CameraArgs c, const uint2* 
 }
 
 void fwd_render(const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img, float* out_color,
-                hipStream_t st, uint32_t* err_host) {
+                hipStream_t st, uint32_t* err_host, const FwdAux& aux) {
   const int tiles = c.gx * c.gy;
   const int blocks = (int)xcd_span((uint32_t)tiles) * 32;
-  if (exact_exp())
-    GS_LAUNCH("render_fwd", k_render_fwd_q<true>, dim3(blocks), dim3(64), 0, st, c, img.ranges, bin.point_list,
-              bin.presort_gid, geo.splat, out_color, img, &geo.counters[CNT_ERR], err_host);
-  else
-    GS_LAUNCH("render_fwd", k_render_fwd_q<false>, dim3(blocks), dim3(64), 0, st, c, img.ranges, bin.point_list,
-              bin.presort_gid, geo.splat, out_color, img, &geo.counters[CNT_ERR], err_host);
+#define GS_FWDQ(NAME, EXACT, AUX)                                                                           \
+  GS_LAUNCH(NAME, (k_render_fwd_q<EXACT, AUX>), dim3(blocks), dim3(64), 0, st, c, img.ranges, bin.point_list, \
+            bin.presort_gid, geo.splat, out_color, img, &geo.counters[CNT_ERR], err_host, aux)
+  if (aux.invdepth || aux.alpha) {  // the aux outputs: the AUX walk (gs_forward_render_aux)
+    if (exact_exp())
+      GS_FWDQ("render_fwd_aux", true, true);
+    else
+      GS_FWDQ("render_fwd_aux", false, true);
+  } else if (exact_exp()) {
+    GS_FWDQ("render_fwd", true, false);
+  } else {
+    GS_FWDQ("render_fwd", false, false);
+  }
+#undef GS_FWDQ
 }
 
 // ------------------------------------------------------------------------------------------

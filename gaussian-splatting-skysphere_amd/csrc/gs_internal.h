@@ -459,12 +459,37 @@ void fwd_bin_views(int views, int P, uint32_t I, const CameraArgs& c, const Geom
                    const ImgPtrs& img, uint64_t geo_stride, uint64_t bin_stride, uint64_t img_stride, hipStream_t st);
 // err_host (device-visible pinned host word, or null): the ordering's error flags, stored by the render
 // when nonzero (the host clears the word before it hands it out)
+// aux outputs of the render (gs_forward_render_aux): [H, W] each, either may be null; both null =
+// the plain kernels
+struct FwdAux {
+  float* invdepth = nullptr;  // sum_i alpha_i T_i / z_i
+  float* alpha = nullptr;     // 1 - final_T
+};
 void fwd_render(const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img, float* out_color,
-                hipStream_t st, uint32_t* err_host = nullptr);
+                hipStream_t st, uint32_t* err_host = nullptr, const FwdAux& aux = FwdAux());
 void mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present,
                   hipStream_t st);
+// aux gradients of the backward (gs_backward_accumulate_aux): dL/dinvdepth and dL/dalpha, [H, W] each,
+// either may be null (zero); gradrec_aux[R] takes each instance's dL/d(1 / z) sum next to its 36-B
+// record, gsum_aux[P] the per-Gaussian sums.  Both gradients null = the plain kernels.
+struct BwdAux {
+  const float* d_invdepth = nullptr;
+  const float* d_alpha = nullptr;
+  float* gradrec_aux = nullptr;
+  float* gsum_aux = nullptr;
+  bool on() const { return d_invdepth || d_alpha; }
+};
+// the grad scratch of the aux backward: [R records of GRAD_REC floats | gradrec_aux[R] | gsum_aux[P]]
+inline size_t grad_layout_aux(size_t R, size_t P, size_t* o_rec_aux, size_t* o_gsum_aux) {
+  size_t off = align_up(R * GRAD_REC * sizeof(float));
+  if (o_rec_aux) *o_rec_aux = off;
+  off += align_up(R * sizeof(float));
+  if (o_gsum_aux) *o_gsum_aux = off;
+  off += align_up(P * sizeof(float));
+  return off;
+}
 void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
-                const float* dL_dpix, float* gradrec, hipStream_t st);
+                const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux = BwdAux());
 struct GradOut {
   float* dmean2D;   // [P, 3]
   float* dcolor;    // [P, 3] or null
@@ -506,7 +531,11 @@ void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin,
                  uint32_t R, bool have_records, float* dmean2D, uint32_t acc, hipStream_t st);
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
-                    bool have_records, const GradOut& out, hipStream_t st);
+                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux = BwdAux());
+// the aux backward's per-Gaussian tail, after the kernel that writes the gradients: the depth
+// chain's add into dL/dmeans3D (from gsum_aux, summed with the other record sums)
+void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BwdAux& aux,
+                     float* dmean3D, hipStream_t st);
 void knn_mean_dist2(int P, const float* pts, float* out, char* scratch, hipStream_t st);
 void ssim_forward(int planes, int H, int W, const float* win11, const float* img1, const float* img2, float* dmaps,
                   float* partial, float* plane_sum, hipStream_t st);

@@ -363,6 +363,51 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     return num_rendered, out_color, radii, geom, binning, img
 
 
+def rasterize_gaussians_aux(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                            viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                            prefiltered, debug, sh_rest=None):
+    """rasterize_gaussians plus the render's aux outputs (gs_forward_render_aux): returns its six
+    values and (invdepth [1, H, W], alpha [1, H, W]).  Always the two-call path over ctypes."""
+    x = _Inputs(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
+                campos, sh_rest=sh_rest)
+    H, W = int(image_height), int(image_width)
+    dev = x.device
+    u8 = dict(dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    if x.P == 0:  # nothing is launched for an empty scene: all-zero outputs
+        return (0, torch.zeros((3, H, W), **f32), torch.zeros((0,), dtype=torch.int32, device=dev),
+                torch.empty((0,), **u8), torch.empty((0,), **u8), torch.empty((0,), **u8),
+                torch.zeros((1, H, W), **f32), torch.zeros((1, H, W), **f32))
+    # every pixel of the three images and every radius is written by the kernels
+    out_color = torch.empty((3, H, W), **f32)
+    invdepth, alpha = torch.empty((1, H, W), **f32), torch.empty((1, H, W), **f32)
+    radii = torch.empty((x.P,), dtype=torch.int32, device=dev)
+    geom = torch.empty((_lib.gs_geom_buffer_bytes(x.P),), **u8)
+    nr = ctypes.c_longlong(0)
+    split = x.sh_rest is not None
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        _native.check(
+            (_lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)(
+                x.P, int(degree), x.M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh),
+                _ptr(x.sh_rest) if split else _ptr(x.colors),
+                _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D),
+                _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
+                int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st),
+            "rasterize_gaussians (preprocess)")
+        num_rendered = int(nr.value)
+        _LAST_NUM_RENDERED[0] = num_rendered
+        binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
+        img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
+        _native.check(
+            _lib.gs_forward_render_aux(
+                x.P, _ptr(x.bg), W, H, _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
+                _ptr(radii), _ptr(geom), num_rendered, _ptr(binning), _ptr(img), _ptr(out_color), _ptr(invdepth),
+                _ptr(alpha), int(bool(debug)), st),
+            "rasterize_gaussians (render, aux outputs)")
+    return num_rendered, out_color, radii, geom, binning, img, invdepth, alpha
+
+
 def binning_layout_count(R, binningBuffer, W, H):
     """The instance count binningBuffer is laid out for, which the C-ABI calls take as num_rendered:
     R for a buffer of gs_binning_buffer_bytes(R) bytes (the two-call, bounded and prepared
@@ -385,7 +430,7 @@ GS_ACC = {n: 1 << k for k, n in enumerate(GRAD_NAMES)}
 
 def backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                   projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                  imageBuffer, debug, want_all=True, sinks=None, wait_event=None, sh_rest=None):
+                  imageBuffer, debug, want_all=True, sinks=None, wait_event=None, sh_rest=None, aux_grads=None):
     """Shared backward.  With want_all=False the gradients that no autograd input can receive
     (colours when SHs drive the colour, cov3D when scale/rotation drive it, ...) are None and
     not computed.  sinks: {name: (buffer, accumulate)} -- that gradient is written into (or, with
@@ -393,8 +438,12 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     (gs_backward_accumulate; multi-view gradient buckets, gs_view_parallel.GradBucket).
     wait_event: torch.cuda.Event the stream waits for before the kernel that writes the gradients
     (a sink shared with views on other streams).  sh_rest: split SH rows as rasterize_gaussians;
-    the `sh` gradient is then that of the concatenation, [P, M, 3]."""
-    if _EXT is not None and not want_all and means3D.is_cuda:
+    the `sh` gradient is then that of the concatenation, [P, M, 3].
+    aux_grads: (dL_dout_invdepth, dL_dout_alpha) of a rasterize_gaussians_aux forward, either may be
+    None (gs_backward_accumulate_aux, over ctypes)."""
+    if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
+        aux_grads = None
+    if _EXT is not None and not want_all and means3D.is_cuda and aux_grads is None:
         return _EXT.backward(background, means3D, radii, colors, scales, rotations, float(scale_modifier),
                              cov3D_precomp, viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color,
                              sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, bool(debug),
@@ -444,6 +493,23 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
         st = _stream(dev)
         grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes(R),), dtype=torch.uint8, device=dev)
         wait = ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None
+        if aux_grads is not None:
+            d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
+            for t in (d_inv, d_alpha):
+                if t is not None and t.numel() != H * W:
+                    raise RuntimeError("aux gradients must have shape (1, H, W)")
+            grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes_aux(R, P),), dtype=torch.uint8, device=dev)
+            _native.check(
+                _lib.gs_backward_accumulate_aux(
+                    P, int(degree), M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh), _ptr(x.sh_rest),
+                    _ptr(x.colors), _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations),
+                    _ptr(x.cov3D), _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
+                    _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix),
+                    _ptr(d_inv), _ptr(d_alpha), _ptr(grad_scratch), _ptr(o["means2D"]), _ptr(o["colors"]),
+                    _ptr(o["opacity"]), _ptr(o["means3D"]), _ptr(o["cov3D"]), _ptr(o["sh"]), _ptr(o["scales"]),
+                    _ptr(o["rotations"]), acc, wait, int(bool(debug)), st),
+                "rasterize_gaussians_backward (aux outputs)")
+            return ret
         if x.sh_rest is not None:  # split SH rows: SH colours, so no dL/dcolors output
             _native.check(
                 _lib.gs_backward_accumulate_split(

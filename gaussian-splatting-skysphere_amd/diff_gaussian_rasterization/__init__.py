@@ -9,6 +9,8 @@ Public surface used by the reference's render adapter
     GaussianRasterizer(raster_settings)(means3D, means2D, opacities, shs=None, colors_precomp=None,
                                         scales=None, rotations=None, cov3D_precomp=None)
         -> (color [3, H, W] fp32, radii [P] int32)
+    GaussianRasterizer(raster_settings)(..., aux_outputs=True)      (extension)
+        -> (color, radii, invdepth [1, H, W] fp32, alpha [1, H, W] fp32)
     GaussianRasterizer.markVisible(positions) -> bool [P]
     rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings)
@@ -18,6 +20,11 @@ un-vendored submodule, /root/reference/.gitmodules:4-6), implemented over libgsr
 HIP for gfx950, C ABI in include/gsrast.h).  Gradients flow to every tensor input that requires
 them, including `means2D`, whose .grad holds the NDC-space screen gradient read by densification
 (/root/reference/scene/gaussian_model.py:405-407).
+
+aux_outputs=True adds two differentiable by-products of the same tile walk (rasterize_gaussians_aux):
+alpha = 1 - final_T, the accumulated opacity (per-pixel backgrounds: color + (1 - alpha) * sky), and
+invdepth = sum_i alpha_i T_i / z_i, the expected inverse depth (depth regularisation).  The default
+call runs the same kernels and gives the same bits as before.
 """
 from __future__ import annotations
 
@@ -29,7 +36,8 @@ import torch.nn as nn
 
 from . import _C
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "cpu_deep_copy_tuple",
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_aux",
+           "cpu_deep_copy_tuple",
            "register_gradient_sink", "unregister_gradient_sink", "prepare_views", "last_num_rendered",
            "bounded_status"]
 
@@ -354,6 +362,121 @@ class _RasterizeGaussians(torch.autograd.Function):
         return tuple(grads)
 
 
+# ------------------------------------------------------------------------------------------
+# Aux outputs (an extension beyond the 2023 upstream API; later upstream revisions return the
+# inverse depth as a third output).  aux_outputs=True: the render's AUX walk also writes
+#   alpha    = 1 - final_T           the accumulated opacity, 0 where no splat reaches the pixel
+#   invdepth = sum_i alpha_i T_i / z_i   the expected inverse depth (no background term)
+# both [1, H, W] and differentiable: alpha is a colour channel of colour 0 and background -1, the
+# inverse depth one of colour 1 / z_i (its gradient also reaches means3D through z_i).  Colour and
+# radii are bit-identical to the plain call's, and a backward that receives no aux gradient runs
+# the plain backward.  Aux calls take the two-call path over ctypes (not _gs_ext); prepared views,
+# bounded forwards and deferring gradient owners are refused.
+# ------------------------------------------------------------------------------------------
+def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                            raster_settings, sh_split=None):
+    """-> (color, radii, invdepth, alpha)"""
+    return _RasterizeGaussiansAux.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                        cov3Ds_precomp, raster_settings, sh_split)
+
+
+class _RasterizeGaussiansAux(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, sh_split=None):
+        s = raster_settings
+        view, proj = _contiguous_matrix(s.viewmatrix), _contiguous_matrix(s.projmatrix)
+        sh_rest = None
+        sh_input = sh
+        if sh_split is not None:  # as _RasterizeGaussians: `sh` is the gradient carrier only
+            dc, sh_rest = (t.detach() for t in sh_split)
+            if tuple(sh.shape) != (dc.shape[0], 1 + sh_rest.shape[1], 3):
+                raise RuntimeError("sh_split: shs must be the [P, M, 3] gradient carrier of cat(features_dc, "
+                                   "features_rest)")
+            sh = dc
+        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                view, proj, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
+                s.campos, s.prefiltered, s.debug)
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, invdepth, alpha = _run_with_snapshot(
+            lambda *a: _C.rasterize_gaussians_aux(*a, sh_rest=sh_rest), args, s.debug, "snapshot_fw.dump", "forward")
+        # the same context as _RasterizeGaussians: a backward without an aux gradient is its backward
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.matrices = (view, proj)
+        ctx.sh_rest = sh_rest
+        ctx.sh_split_versions = None if sh_rest is None else (sh._version, sh_rest._version)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
+                              binningBuffer, imgBuffer)
+        ctx.mark_non_differentiable(radii)
+        sinks = []
+        if _SINKS:
+            inputs = (means3D, means2D, sh_input, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+            for k, name in _SINK_INPUTS:
+                owner = _sink_owner(inputs[k])
+                if owner is not None:
+                    sinks.append((k, name, inputs[k], owner))
+            for owner in {id(o): o for _k, _n, _t, o in sinks}.values():
+                if hasattr(owner, "forwarded"):
+                    owner.forwarded(geomBuffer, means3D.shape[0])
+        ctx.sinks = sinks
+        return color, radii, invdepth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_invdepth, grad_alpha):
+        if grad_invdepth is None and grad_alpha is None:
+            # only the colour reached the loss (or nothing did): the plain backward, as it stands
+            return tuple(_RasterizeGaussians.backward(ctx, grad_out_color, None)[:8]) + (None, None)
+        s = ctx.raster_settings
+        if _deferring_owner(ctx) is not None:
+            raise RuntimeError("aux_outputs: an alpha / inverse-depth gradient is not supported with a deferring "
+                               "gradient owner (GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = (
+            ctx.saved_tensors)
+        if ctx.sh_rest is not None and (sh._version, ctx.sh_rest._version) != ctx.sh_split_versions:
+            raise RuntimeError("sh_split: features_dc or features_rest was modified by an inplace operation between "
+                               "the forward and the backward")
+        view, proj = ctx.matrices
+        if grad_out_color is None:  # the loss reads the aux outputs only
+            grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32,
+                                         device=means3D.device)
+        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                view, proj, s.tanfovx, s.tanfovy, grad_out_color.contiguous(), sh, s.sh_degree,
+                s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
+        # gradient sinks and their write order, as in _RasterizeGaussians.backward
+        sinks, sunk, owners = {}, set(), []
+        for k, name, t, owner in ctx.sinks:
+            if ctx.needs_input_grad[k]:
+                claim = owner.claim(t)
+                if claim is not None:
+                    sinks[name] = claim
+                    sunk.add(k)
+                    if all(o is not owner for o in owners):
+                        owners.append(owner)
+        wait = None
+        if owners:
+            st = torch.cuda.current_stream(grad_out_color.device)
+            evs = [e for e in (o.write_order(st) for o in owners if hasattr(o, "write_order")) if e is not None]
+            for e in evs[1:]:
+                st.wait_event(e)
+            wait = evs[0] if evs else None
+
+        def _bwd(*a):
+            return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
+                                    aux_grads=(grad_invdepth, grad_alpha))
+
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations) = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+        for o in owners:
+            if hasattr(o, "written"):
+                o.written(st)
+        grads = [grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
+                 grad_rotations, grad_cov3Ds_precomp, None, None]
+        for k in sunk:
+            grads[k] = None
+        return tuple(grads)
+
+
 def _deferring_owner(ctx):
     """The one sink owner with `defer_view` that receives every input gradient this backward must
     produce (means2D aside), or None."""
@@ -380,15 +503,22 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, prepared=None, sh_split=None, binning_capacity=None):
+                cov3D_precomp=None, prepared=None, sh_split=None, binning_capacity=None, aux_outputs=False):
         """prepared: this call's PreparedView from prepare_views (extension; default: none).
         binning_capacity: size the binning buffer for that many instances and run the forward
         without a host wait (extension, ABI v10; see bounded_status()).
         sh_split: (features_dc [P,1,3], features_rest [P,M-1,3]) read in place instead of the
         concatenated shs (extension, ABI v8: no per-iteration cat); `shs` is then a [P,M,3] tensor
         whose values are never read and whose .grad receives dL/d cat(features_dc, features_rest)
-        (what FusedAdam.step_activated consumes).  Bit-identical to passing the concatenation."""
+        (what FusedAdam.step_activated consumes).  Bit-identical to passing the concatenation.
+        aux_outputs: also return the expected inverse depth and the accumulated opacity of the same
+        walk, (color, radii, invdepth [1,H,W], alpha [1,H,W]), both differentiable (extension; not
+        with prepared= or binning_capacity=)."""
         s = self.raster_settings
+        if aux_outputs and prepared is not None:
+            raise RuntimeError("aux_outputs: not supported with prepared views (prepared=)")
+        if aux_outputs and binning_capacity is not None:
+            raise RuntimeError("aux_outputs: not supported with a bounded forward (binning_capacity=)")
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
@@ -400,5 +530,8 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        if aux_outputs:
+            return rasterize_gaussians_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                           cov3D_precomp, s, sh_split)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    s, prepared, sh_split, binning_capacity)

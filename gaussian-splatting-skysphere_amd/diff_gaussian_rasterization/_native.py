@@ -141,6 +141,19 @@ SIGNATURES = {
     "gs_geom_flags_offset": (_c_sz, [_c_i]),
     "gs_forward_order_status": (_c_i, []),
     "gs_set_row_waits": (_c_i, [_c_i, _c_p, _c_p]),
+    # GSRAST_HAS_AUX: the alpha / inverse-depth outputs of the render and their gradients
+    "gs_grad_buffer_bytes_aux": (_c_sz, [_c_ll, _c_i]),
+    "gs_forward_render_aux": (
+        _c_i,
+        [_c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i,
+         _c_p],
+    ),
+    "gs_backward_accumulate_aux": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_p, ctypes.c_uint, _c_p, _c_i, _c_p],
+    ),
     "gs_mark_visible": (_c_i, [_c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gs_knn_scratch_bytes": (_c_sz, [_c_i]),
     "gs_knn_mean_dist2": (_c_i, [_c_i, _c_p, _c_p, _c_p, _c_p]),

@@ -61,6 +61,10 @@ extern "C" {
 
 #define GSRAST_ABI_VERSION 17  /* v17: gs_geom_flags_offset, gs_forward_order_status, gs_set_row_waits; v16: gs_backward_gaussians_adam_stats (v15: gs_backward_gaussians_adam; v14: gs_forward_counted + gs_binning_layout_count) */
 
+/* Aux render outputs (additive, same ABI version): gs_grad_buffer_bytes_aux, gs_forward_render_aux,
+ * gs_backward_accumulate_aux. */
+#define GSRAST_HAS_AUX 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -69,6 +73,9 @@ size_t gs_geom_buffer_bytes(int P);
 size_t gs_binning_buffer_bytes(long long num_rendered, int image_width, int image_height);
 size_t gs_image_buffer_bytes(int image_width, int image_height);
 size_t gs_grad_buffer_bytes(long long num_rendered);
+/* Grad scratch of gs_backward_accumulate_aux: the records of gs_grad_buffer_bytes(num_rendered), then
+ * one float per instance slot (dL/d(1/z) of the instance) and one float per Gaussian (their sums). */
+size_t gs_grad_buffer_bytes_aux(long long num_rendered, int P);
 /* The instance count a binning buffer of `bytes` bytes is laid out for: the largest n with
  * gs_binning_buffer_bytes(n, W, H) <= bytes (every such n gives the same layout).  A buffer that
  * gs_forward_counted filled for `capacity` instances goes to the backward with this count in place
@@ -110,6 +117,23 @@ int gs_forward_render(int P, const float* background, int image_width, int image
                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                       float tan_fovy, const int* radii, void* geom_buffer, long long num_rendered,
                       void* binning_buffer, void* image_buffer, float* out_color, int debug, void* stream);
+
+/* ---- forward, part 2 with the aux outputs (GSRAST_HAS_AUX) ----
+ * gs_forward_render plus two per-pixel by-products of the same tile walk, [H, W] fp32 each, either
+ * may be NULL:
+ *   out_alpha[p]    = 1.0f - final_T(p), the accumulated opacity (0 for a pixel no splat reaches);
+ *   out_invdepth[p] = sum_i (1 / z_i) alpha_i T_i, the expected inverse depth, z_i the view depth of
+ *                     splat i, composited in the form and order of a colour channel (exact mode:
+ *                     acc + (c alpha) T; fast mode: fma(c, alpha T, acc)), with no background term.
+ * alpha_i, T_i and every decision are those of the colour walk; everything else this call writes
+ * (out_color, radii-dependent binning, the image buffer) is what gs_forward_render writes, bit for
+ * bit.  With both NULL it is gs_forward_render.  Second half after gs_forward_preprocess or
+ * gs_forward_preprocess_split. */
+int gs_forward_render_aux(int P, const float* background, int image_width, int image_height,
+                          const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                          float tan_fovy, const int* radii, void* geom_buffer, long long num_rendered,
+                          void* binning_buffer, void* image_buffer, float* out_color, float* out_invdepth,
+                          float* out_alpha, int debug, void* stream);
 
 /* ---- forward in one call without a host wait (bounded binning buffer) ----
  * Both halves of gs_forward_preprocess + gs_forward_render, enqueued without reading num_rendered
@@ -271,6 +295,28 @@ int gs_backward_accumulate(int P, int D, int M, const float* background, int ima
                            void* grad_buffer, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                            float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                            float* dL_drotations, unsigned accumulate, void* wait_event, int debug, void* stream);
+
+/* ---- backward with the aux outputs' gradients (GSRAST_HAS_AUX) ----
+ * gs_backward_accumulate for a forward of gs_forward_render_aux: shs_rest as in gs_forward_bounded
+ * (NULL, or the split rows with shs = features_dc), and dL_dout_invdepth / dL_dout_alpha [H, W], either
+ * may be NULL (zero).  grad_buffer >= gs_grad_buffer_bytes_aux(num_rendered, P).  Alpha enters the
+ * walk as a colour channel of colour 0 and background -1, the inverse depth as one of colour 1 / z_i
+ * and background 0; its per-Gaussian sum s9 = dL/d(1 / z_i) gives dL/dz_i = -s9 / z_i^2, which a small
+ * kernel adds into dL_dmeans3D (fp32 old + new) along (view[2], view[6], view[10]) after the kernel
+ * that writes the gradients.  Same `accumulate` bits and wait_event rule.  With both aux gradients
+ * NULL it runs exactly gs_backward_accumulate (/ _split): same launches, same bits. */
+int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int image_width, int image_height,
+                               const float* means3D, const float* shs, const float* shs_rest,
+                               const float* colors_precomp, const float* opacities, const float* scales,
+                               float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos,
+                               float tan_fovx, float tan_fovy, const int* radii, const void* geom_buffer,
+                               long long num_rendered, const void* binning_buffer, const void* image_buffer,
+                               const float* dL_dout_color, const float* dL_dout_invdepth,
+                               const float* dL_dout_alpha, void* grad_buffer, float* dL_dmeans2D,
+                               float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
+                               float* dL_dsh, float* dL_dscales, float* dL_drotations, unsigned accumulate,
+                               void* wait_event, int debug, void* stream);
 
 /* ---- split SH rows (ABI v8, an extension beyond upstream) ----
  * render() concatenates GaussianModel's features_dc [P,1,3] and features_rest [P,M-1,3] into shs
