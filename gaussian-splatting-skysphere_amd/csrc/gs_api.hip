@@ -1405,6 +1405,40 @@ int gs_ssim_backward(int planes, int channels, int H, int W, const float* window
   return t_failed ? 1 : 0;
 }
 
+/* ---- skysphere background (GSRAST_HAS_SKY) ---- */
+size_t gs_sky_scratch_bytes(int Hs, int Ws) { return Hs > 0 && Ws > 0 ? sky_scratch_bytes(Hs, Ws) : 0; }
+
+static bool sky_shape_ok(int W, int H, int Hs, int Ws) {
+  if (W < 1 || H < 1) return set_error("sky: image size must be positive (got %d x %d)", W, H), false;
+  if (Hs < 1 || Ws < 1) return set_error("sky: texture size must be positive (got %d x %d)", Ws, Hs), false;
+  if (Hs > SKY_MAX_TEX || Ws > SKY_MAX_TEX) return set_error("sky: texture side above %d texels", SKY_MAX_TEX), false;
+  return true;
+}
+
+int gs_sky_compose_forward(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
+                           const float* texture, const float* color, const float* alpha, float* out_image,
+                           void* stream) {
+  clear_error(0);
+  if (!sky_shape_ok(W, H, Hs, Ws)) return 1;
+  if (!viewmatrix || !texture || !out_image) return set_error("sky: missing pointer"), 1;
+  sky_forward(W, H, viewmatrix, tanfovx, tanfovy, Hs, Ws, texture, color, alpha, out_image, (hipStream_t)stream);
+  return t_failed ? 1 : 0;
+}
+
+int gs_sky_compose_backward(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
+                            const float* texture, const float* alpha, const float* dL_dimage, float* dL_dalpha,
+                            float* dL_dtexture, int accumulate_texture, void* scratch, void* stream) {
+  clear_error(0);
+  if (!sky_shape_ok(W, H, Hs, Ws)) return 1;
+  if (!viewmatrix || !texture || !dL_dimage) return set_error("sky: missing pointer"), 1;
+  if (dL_dtexture && !scratch) return set_error("sky: dL_dtexture needs the scratch of gs_sky_scratch_bytes"), 1;
+  if (dL_dtexture && (((uintptr_t)scratch) & 15)) return set_error("sky: scratch must be 16-byte aligned"), 1;
+  if (!dL_dalpha && !dL_dtexture) return 0;
+  sky_backward(W, H, viewmatrix, tanfovx, tanfovy, Hs, Ws, texture, alpha, dL_dimage, dL_dalpha, dL_dtexture,
+               accumulate_texture != 0, (char*)scratch, (hipStream_t)stream);
+  return t_failed ? 1 : 0;
+}
+
 /* ---- fused photometric loss (train.py:91-92) ---- */
 int gs_photometric_loss_forward(int planes, int H, int W, const float* window11_host, const float* img,
                                 const float* gt, float lambda_dssim, float* dmaps, float* partial, float* out3,

@@ -546,6 +546,14 @@ void photometric_forward(int planes, int H, int W, const float* win11, const flo
                          float lambda, float* dmaps, float* partial, float* out3, hipStream_t st);
 void photometric_backward(int planes, int H, int W, const float* win11, const float* img, const float* gt,
                           const float* dmaps, float lambda, const float* grad, float* dimg, hipStream_t st);
+// ---- skysphere background (gs_sky.hip): equirect texture sampled along the pixel rays ----
+constexpr int SKY_MAX_TEX = 1 << 24;  // texture rows / columns: texel indices stay exact in fp32
+size_t sky_scratch_bytes(int Hs, int Ws);
+void sky_forward(int W, int H, const float* view, float tanfovx, float tanfovy, int Hs, int Ws, const float* tex,
+                 const float* color, const float* alpha, float* out, hipStream_t st);
+void sky_backward(int W, int H, const float* view, float tanfovx, float tanfovy, int Hs, int Ws, const float* tex,
+                  const float* alpha, const float* dimage, float* dalpha, float* dtex, bool accumulate, char* scratch,
+                  hipStream_t st);
 constexpr int ADAM_MAX_TENSORS = 16;  // parameter tensors per Adam launch
 // ---- Adam (torch.optim.Adam semantics), shared by k_adam and the fused per-Gaussian backward ----
 struct AdamConsts {

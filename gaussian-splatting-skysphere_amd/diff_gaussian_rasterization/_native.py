@@ -154,6 +154,11 @@ SIGNATURES = {
          _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
          _c_p, ctypes.c_uint, _c_p, _c_i, _c_p],
     ),
+    # GSRAST_HAS_SKY: the skysphere background and its gradients
+    "gs_sky_scratch_bytes": (_c_sz, [_c_i, _c_i]),
+    "gs_sky_compose_forward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "gs_sky_compose_backward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i,
+                                       _c_p, _c_p]),
     "gs_mark_visible": (_c_i, [_c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gs_knn_scratch_bytes": (_c_sz, [_c_i]),
     "gs_knn_mean_dist2": (_c_i, [_c_i, _c_p, _c_p, _c_p, _c_p]),

@@ -65,6 +65,10 @@ extern "C" {
  * gs_backward_accumulate_aux. */
 #define GSRAST_HAS_AUX 1
 
+/* Skysphere background (additive, same ABI version): gs_sky_scratch_bytes, gs_sky_compose_forward,
+ * gs_sky_compose_backward. */
+#define GSRAST_HAS_SKY 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -443,6 +447,32 @@ int gs_photometric_loss_forward(int planes, int H, int W, const float* window11_
 int gs_photometric_loss_backward(int planes, int H, int W, const float* window11_host, const float* img,
                                  const float* gt, const float* dmaps, float lambda_dssim, const float* grad,
                                  float* dimg, void* stream);
+
+/* ---- skysphere background (GSRAST_HAS_SKY, an extension beyond the reference) ----
+ * A learnable equirectangular texture[3, Hs, Ws] (fp32 CHW, texel centres at half-integers) sampled
+ * along every pixel's camera ray and composited behind the splats:
+ *   out_image[c, y, x] = color[c, y, x] + (1 - alpha[y, x]) * sky_c(x, y).
+ * Pixel (x, y), integer coordinates at pixel centres as in the rasterizer's projection:
+ *   d_cam = (((2x + 1) / W - 1) tanfovx, ((2y + 1) / H - 1) tanfovy, 1),  d_i = sum_j V[i][j] d_cam_j
+ *   (V = viewmatrix, the forward's device [4, 4]);  u = atan2(d.x, d.z) / 2pi + 0.5,
+ *   v = acos(clamp(-d.y / |d|, -1, 1)) / pi (row 0 is world -y);  tx = u Ws - 0.5, ty = v Hs - 0.5;
+ *   bilinear over columns floor(tx), floor(tx) + 1 (wrapping modulo Ws) and rows floor(ty),
+ *   floor(ty) + 1 (clamped to [0, Hs - 1]).
+ * Forward: color == NULL is a colour of 0, alpha == NULL an alpha of 0 (both NULL: the bare sky).
+ * Backward, with g = dL_dimage[3, H, W] (dL/dcolor is g itself):
+ *   dL_dalpha[y, x] = -sum_c g_c sky_c (NULL: not produced);
+ *   dL_dtexture[c, texel] = sum over pixels of g_c (1 - alpha) w_texel (NULL: not produced), written
+ *   (accumulate_texture 0) or added as fp32 old + new (1).  The sums are formed in 64-bit fixed point
+ *   with integer atomics, so they are bit-identical from run to run; scratch holds
+ *   gs_sky_scratch_bytes(Hs, Ws) bytes (16-byte aligned; needed only with dL_dtexture).
+ * Nothing is kept between the two calls: the backward recomputes the rays. */
+size_t gs_sky_scratch_bytes(int Hs, int Ws);
+int gs_sky_compose_forward(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
+                           const float* texture, const float* color, const float* alpha, float* out_image,
+                           void* stream);
+int gs_sky_compose_backward(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
+                            const float* texture, const float* alpha, const float* dL_dimage, float* dL_dalpha,
+                            float* dL_dtexture, int accumulate_texture, void* scratch, void* stream);
 
 /* ---- fused Adam step  <-  torch.optim.Adam.step() of GaussianModel's optimizer
  *      (/root/reference/scene/gaussian_model.py:154-163, stepped at train.py:123-124) ----
