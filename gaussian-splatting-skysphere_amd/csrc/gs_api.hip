@@ -137,26 +137,60 @@ static CameraArgs make_camera(const float* bg, int W, int H, const float* view, 
   return c;
 }
 
-static bool validate(int P, int D, int M, int W, int H, const float* means3D, const float* shs, const float* colors,
-                     const float* opac, const float* scales, const float* rots, const float* cov3D, const float* view,
-                     const float* proj, const float* campos, const float* bg, bool need_opac = true) {
-  if (P < 0) return set_error("P must be >= 0"), false;
-  if (W <= 0 || H <= 0) return set_error("image size must be positive (got %d x %d)", W, H), false;
-  if (P == 0) return true;
-  if (!means3D || (need_opac && !opac) || !view || !proj || !bg)
-    return set_error("missing required input pointer"), false;
-  if ((shs == nullptr) == (colors == nullptr))
-    return set_error("Please provide excatly one of either SHs or precomputed colors!"), false;
-  if (((scales == nullptr || rots == nullptr) && cov3D == nullptr) || ((scales || rots) && cov3D))
-    return set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!"), false;
-  if (shs) {
-    if (D < 0 || D > 3) return set_error("SH degree must be in [0, 3] (got %d)", D), false;
-    if (M < (D + 1) * (D + 1)) return set_error("shs has %d coefficients, degree %d needs %d", M, D, (D + 1) * (D + 1)), false;
-    if (!campos) return set_error("campos is required with SHs"), false;
+// a camera that carries an image size only (the buffer layouts and the binning read nothing else)
+static CameraArgs size_camera(int W, int H) {
+  return make_camera(nullptr, W, H, nullptr, nullptr, nullptr, 1.0f, 1.0f, 0);
+}
+
+// The scene of a call, packed once at the ABI boundary, in the entries' own argument order
+// (shs_rest: the split SH rows, null in the entries without them).
+static GaussianArgs make_scene(int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest,
+                               const float* colors, const float* opacities, const float* scales, float scale_modifier,
+                               const float* rotations, const float* cov3D) {
+  return GaussianArgs{P, D, M, means3D, shs, colors, opacities, scales, rotations, cov3D, scale_modifier, shs_rest};
+}
+
+// The scene and camera checks of every forward / backward entry.  Their order is part of the
+// contract (which of two faults is reported; tests/test_api_contract_cpu.py pins it).
+static bool validate(const GaussianArgs& g, const CameraArgs& c, bool need_opac = true) {
+  if (g.P < 0) return set_error("P must be >= 0"), false;
+  if (c.W <= 0 || c.H <= 0) return set_error("image size must be positive (got %d x %d)", c.W, c.H), false;
+  if (g.P > 0) {
+    if (!g.means3D || (need_opac && !g.opacities) || !c.view || !c.proj || !c.bg)
+      return set_error("missing required input pointer"), false;
+    if ((g.shs == nullptr) == (g.colors == nullptr))
+      return set_error("Please provide excatly one of either SHs or precomputed colors!"), false;
+    if (((g.scales == nullptr || g.rotations == nullptr) && g.cov3D == nullptr) ||
+        ((g.scales || g.rotations) && g.cov3D))
+      return set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!"), false;
+    if (g.shs) {
+      if (g.D < 0 || g.D > 3) return set_error("SH degree must be in [0, 3] (got %d)", g.D), false;
+      if (g.M < (g.D + 1) * (g.D + 1))
+        return set_error("shs has %d coefficients, degree %d needs %d", g.M, g.D, (g.D + 1) * (g.D + 1)), false;
+      if (!c.campos) return set_error("campos is required with SHs"), false;
+    }
+    if ((size_t)g.P * 48 > ((size_t)1 << 40)) return set_error("P too large"), false;
   }
-  if ((size_t)P * 48 > ((size_t)1 << 40)) return set_error("P too large"), false;
+  // split SH inputs (features_dc + features_rest rows; also checked for an empty scene): shs_rest
+  // needs SH colours with M >= 2
+  if (!g.shs_rest) return true;
+  if (!g.shs || g.colors) return set_error("split SH: features_dc and features_rest replace shs (no colours)"), false;
+  if (g.M < 2) return set_error("split SH: M must be >= 2 (got %d)", g.M), false;
   return true;
 }
+
+// The three buffers of a view laid out: P Gaussians, I instances, the camera's image size
+// (a null base pointer leaves that part unset).
+struct Layouts {
+  GeomPtrs geo;
+  BinPtrs bin;
+  ImgPtrs img;
+  Layouts(int P, long long I, const CameraArgs& c, const void* geom, const void* binning, const void* image) {
+    geom_layout((size_t)P, &geo, (char*)geom);
+    bin_layout((size_t)I, c.gx * c.gy, &bin, (char*)binning);
+    img_layout(c.W, c.H, &img, (char*)image);
+  }
+};
 
 // ------------------------------------------------------------------------------------------
 // debug export kernel
@@ -483,50 +517,114 @@ static bool bounded_status_error(uint32_t f, long long inst) {
   return false;
 }
 
-// split SH inputs (features_dc + features_rest rows): shs_rest needs SH colours with M >= 2
-static bool validate_split(int M, const float* shs, const float* shs_rest, const float* colors_precomp) {
-  if (!shs_rest) return true;
-  if (!shs || colors_precomp) return set_error("split SH: features_dc and features_rest replace shs (no colours)"), false;
-  if (M < 2) return set_error("split SH: M must be >= 2 (got %d)", M), false;
-  return true;
+// the status words for a new bounded forward, once an earlier one's flags are reported; null: error set
+static BoundedStatus* bounded_status_checked() {
+  BoundedStatus* bs = bounded_status();
+  long long inst = 0;
+  return bs && !bounded_status_error(take_bounded_status(bs, &inst), inst) ? bs : nullptr;
 }
 
-static int forward_preprocess_impl(int P, int D, int M, const float* background, int W, int H, const float* means3D,
-                                   const float* shs, const float* shs_rest, const float* colors_precomp,
-                                   const float* opacities, const float* scales, float scale_modifier,
-                                   const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                                   const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                                   int prefiltered, int* radii_out, void* geom_buffer, long long* num_rendered_host,
-                                   int debug, void* stream) {
+// ---- forward: each entry packs its arguments once (make_scene, make_camera, FwdOut) and runs shared steps ----
+// What a single-view forward writes (the preprocess entries: radii and geom only)
+struct FwdOut {
+  int* radii;  // written by the preprocess, read by the binning
+  void* geom;
+  long long num_rendered;  // the instance count the binning buffer is laid out for (bounded / counted: the capacity)
+  void* binning;
+  void* image;
+  float* out_color;
+  FwdAux aux;
+};
+
+// The render tail: the binning (TAIL_BIN) and the compositing of a view whose ordering is queued.
+// TAIL_BOUNDED: the ordering's error flags go to the sticky bounded-status word, nothing is
+// recorded or checked here.  The caller has checked the arguments.
+enum : unsigned { TAIL_BIN = 1u, TAIL_BOUNDED = 2u };
+static int render_tail(int P, const CameraArgs& c, const FwdOut& o, unsigned mode, hipStream_t st,
+                       unsigned long long* oseq_out = nullptr) {
+  const bool bounded = (mode & TAIL_BOUNDED) != 0;
+  const Layouts L(P, o.num_rendered, c, o.geom, o.binning, o.image);
+  // the look-back waits of the offsets scan and of the one-sweep sorts (never expected to run out:
+  // the waited-for workgroups are running) leave ERR_LOOKBACK; the render kernel stores the flags
+  // into pinned memory, behind an event that the next backward or forward call checks, so no host
+  // wait idles the device
+  BoundedStatus* bs = bounded ? bounded_status() : nullptr;
+  unsigned long long oseq = 0;
+  uint32_t* flags_word = bounded ? (bs ? bs->dev + 4 : nullptr) : order_flags_word(&oseq);
+  if (!flags_word) return 1;
+  if (mode & TAIL_BIN) fwd_bin(P, (uint32_t)o.num_rendered, c, o.radii, L.geo, L.bin, L.img, st);
+  fwd_render(c, L.geo, L.bin, L.img, o.out_color, st, flags_word, o.aux);
+  if (!bounded) {
+    if (oseq_out) *oseq_out = oseq;
+    if (t_failed) release_order_word(oseq);
+    else if (queue_order_flags(st, oseq)) return 1;
+  }
+  return t_failed ? 1 : 0;
+}
+
+// Where a single-view forward's instance totals go: read back before the binning buffer is sized
+// (gs_forward_preprocess: the call ends behind the ordering), into the sticky bounded-status words
+// (gs_forward_bounded: no host wait), or read back at the end of a whole forward that is queued
+// against a capacity meanwhile (gs_forward_counted).
+enum class Totals { ReadBack, Bounded, Counted };
+// The single-view forward: validation, the preprocess and the ordering, then what `mode` asks for.
+// The order of the checks and of their side effects is part of the contract.
+static int forward_view(const GaussianArgs& g, const CameraArgs& c, const FwdOut& o, Totals mode,
+                        long long* num_rendered_host, int debug, hipStream_t st) {
+  const int P = g.P;
+  const bool whole = mode != Totals::ReadBack;  // the binning and the render follow in this call
   clear_error(debug);
-  if (num_rendered_host) *num_rendered_host = 0;
-  if (!validate(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
-                projmatrix, campos, background))
-    return 1;
-  if (!validate_split(M, shs, shs_rest, colors_precomp)) return 1;
+  if (mode != Totals::Bounded && num_rendered_host) *num_rendered_host = 0;
+  if (!validate(g, c)) return 1;
   if (P == 0) return 0;
-  if (!radii_out || !geom_buffer || !num_rendered_host) return set_error("missing output pointer"), 1;
-  hipStream_t st = (hipStream_t)stream;
+  if (whole && (o.num_rendered < 0 || o.num_rendered > GS_MAX_INSTANCES)) return set_error("capacity out of range"), 1;
+  if (!o.radii || !o.geom || (mode != Totals::Bounded && !num_rendered_host) ||
+      (whole && (!o.binning || !o.image || !o.out_color)))
+    return set_error(whole ? "missing buffer pointer" : "missing output pointer"), 1;
+  BoundedStatus* bs = nullptr;
+  ReadbackSlot* rb = nullptr;
+  if (mode == Totals::Bounded) {
+    if (!(bs = bounded_status_checked())) return 1;
+  } else {
+    // num_rendered is the sum of the per-Gaussian tile counts, known when the first depth-sort
+    // histogram launch has summed the preprocess workgroups' totals: that launch stores it straight
+    // into pinned memory, and the host waits for it while the GPU goes on with the depth sort and
+    // the instance offsets (Counted: the binning and the render too), so the round trip overlaps device work.
+    if (!(rb = readback_slot())) return 1;
+    // earlier forwards' look-back waits: the finished ones now (no wait before the launches), then,
+    // after this forward's own readback (behind them on the stream), the rest
+    if (check_order_flags(false)) return 1;
+  }
   GeomPtrs geo;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  GaussianArgs g{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier,
-                 shs_rest};
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered);
-  // num_rendered is the sum of the per-Gaussian tile counts, known when the first depth-sort
-  // histogram launch has summed the preprocess workgroups' totals: that launch stores it straight
-  // into pinned memory, and the host waits for it while the GPU goes on with the depth sort and
-  // the instance offsets, so the host round trip overlaps device work.
-  ReadbackSlot* rb = readback_slot();
-  if (!rb) return 1;
-  // earlier forwards' look-back waits: the finished ones now (no wait before the launches), then,
-  // after this forward's own readback (behind them on the stream), the rest
-  if (check_order_flags(false)) return 1;
-  fwd_preprocess(g, c, radii_out, geo, st);
-  fwd_order(P, geo, st, rb->dev, rb->ev[0]);
-  check_hip(hipEventSynchronize(rb->ev[0]), "hipEventSynchronize");
-  if (t_failed) return 1;
-  if (check_order_flags()) return 1;
-  return read_view_totals(rb->host, 0, 1, num_rendered_host) ? 0 : 1;
+  geom_layout((size_t)P, &geo, (char*)o.geom);
+  fwd_preprocess(g, c, o.radii, geo, st);
+  const uint32_t cap32 = (uint32_t)o.num_rendered;
+  fwd_order(P, geo, st, rb ? rb->dev : nullptr, rb ? rb->ev[0] : nullptr, whole ? &cap32 : nullptr,
+            bs ? bs->dev : nullptr);
+  if (mode == Totals::Bounded) return t_failed ? 1 : render_tail(P, c, o, TAIL_BIN | TAIL_BOUNDED, st);
+  // the count readback is queued into this thread's slot: every return from here on waits for it,
+  // so no kernel of this call can still write the slot's words when the thread's next call reads them
+  auto drain = [&]() { (void)hipEventSynchronize(rb->ev[0]); };
+  if (t_failed) return drain(), 1;
+  unsigned long long oseq = 0;
+  if (whole && render_tail(P, c, o, TAIL_BIN, st, &oseq)) return drain(), 1;
+  if (!check_hip(hipEventSynchronize(rb->ev[0]), "hipEventSynchronize")) return 1;
+  // the rest of the earlier forwards (Counted: but this one, whose render was just queued)
+  if (check_order_flags(true, whole ? (long long)oseq : -1)) return 1;
+  long long I = 0;
+  if (!read_view_totals(rb->host, 0, 1, &I)) return 1;
+  *num_rendered_host = I;
+  if (whole && I > o.num_rendered) {
+    // the queued binning and render skipped their work (ERR_CAPACITY): clear the flag so that
+    // gs_forward_render can bin the same geometry into a buffer of the exact size
+    fwd_clear_flags(geo, ERR_CAPACITY, st);
+    // the skipped render carries this ordering's look-back flags: read them now (it finishes
+    // quickly, having skipped its work), so a timed-out ordering fails here, once, instead of
+    // again at the next call through the re-binned forward's flags
+    if (t_failed || check_order_seq(oseq)) return 1;
+    return GS_COUNT_SHORT;
+  }
+  return 0;
 }
 
 int gs_forward_preprocess(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -535,9 +633,11 @@ int gs_forward_preprocess(int P, int D, int M, const float* background, int W, i
                           const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                           float tan_fovy, int prefiltered, int* radii_out, void* geom_buffer,
                           long long* num_rendered_host, int debug, void* stream) {
-  return forward_preprocess_impl(P, D, M, background, W, H, means3D, shs, nullptr, colors_precomp, opacities, scales,
-                                 scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                 tan_fovy, prefiltered, radii_out, geom_buffer, num_rendered_host, debug, stream);
+  return forward_view(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered),
+      FwdOut{radii_out, geom_buffer}, Totals::ReadBack, num_rendered_host, debug, (hipStream_t)stream);
 }
 
 int gs_forward_preprocess_split(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -551,9 +651,97 @@ int gs_forward_preprocess_split(int P, int D, int M, const float* background, in
     if (num_rendered_host) *num_rendered_host = 0;
     return set_error("split SH: features_rest is NULL"), 1;
   }
-  return forward_preprocess_impl(P, D, M, background, W, H, means3D, shs_dc, shs_rest, nullptr, opacities, scales,
-                                 scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                 tan_fovy, prefiltered, radii_out, geom_buffer, num_rendered_host, debug, stream);
+  return forward_view(
+      make_scene(P, D, M, means3D, shs_dc, shs_rest, nullptr, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered),
+      FwdOut{radii_out, geom_buffer}, Totals::ReadBack, num_rendered_host, debug, (hipStream_t)stream);
+}
+
+// gs_forward_render and its variants: the tail behind its own checks (only the binning needs radii)
+static int forward_render(int P, const CameraArgs& c, const FwdOut& o, unsigned mode, int debug, hipStream_t st) {
+  clear_error(debug);
+  if (P <= 0) return 0;
+  if (c.W <= 0 || c.H <= 0) return set_error("image size must be positive"), 1;
+  if (o.num_rendered < 0 || o.num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
+  if (!o.geom || !o.binning || !o.image || !o.out_color || ((mode & TAIL_BIN) && !o.radii))
+    return set_error("missing buffer pointer"), 1;
+  return render_tail(P, c, o, mode, st);
+}
+// (the render reads the radii; FwdOut carries them as the preprocess writes them)
+static FwdOut render_out(const int* radii, void* geom, long long num_rendered, void* binning, void* image,
+                         float* out_color, float* invdepth = nullptr, float* alpha = nullptr) {
+  return FwdOut{const_cast<int*>(radii), geom, num_rendered, binning, image, out_color, FwdAux{invdepth, alpha}};
+}
+
+int gs_forward_render(int P, const float* background, int W, int H, const float* viewmatrix, const float* projmatrix,
+                      const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
+                      long long num_rendered, void* binning_buffer, void* image_buffer, float* out_color, int debug,
+                      void* stream) {
+  return forward_render(P, make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+                        render_out(radii, geom_buffer, num_rendered, binning_buffer, image_buffer, out_color),
+                        TAIL_BIN, debug, (hipStream_t)stream);
+}
+
+int gs_forward_render_aux(int P, const float* background, int W, int H, const float* viewmatrix,
+                          const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                          const int* radii, void* geom_buffer, long long num_rendered, void* binning_buffer,
+                          void* image_buffer, float* out_color, float* out_invdepth, float* out_alpha, int debug,
+                          void* stream) {
+  return forward_render(P, make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+                        render_out(radii, geom_buffer, num_rendered, binning_buffer, image_buffer, out_color,
+                                   out_invdepth, out_alpha),
+                        TAIL_BIN, debug, (hipStream_t)stream);
+}
+
+int gs_forward_render_bounded(int P, const float* background, int W, int H, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                              const int* radii, void* geom_buffer, long long capacity, void* binning_buffer,
+                              void* image_buffer, float* out_color, int debug, void* stream) {
+  return forward_render(P, make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+                        render_out(radii, geom_buffer, capacity, binning_buffer, image_buffer, out_color),
+                        TAIL_BIN | TAIL_BOUNDED, debug, (hipStream_t)stream);
+}
+
+int gs_forward_render_binned(int P, const float* background, int W, int H, const float* viewmatrix,
+                             const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                             void* geom_buffer, long long num_rendered, void* binning_buffer, void* image_buffer,
+                             float* out_color, int bounded, int debug, void* stream) {
+  return forward_render(P, make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+                        render_out(nullptr, geom_buffer, num_rendered, binning_buffer, image_buffer, out_color),
+                        bounded ? TAIL_BOUNDED : 0u, debug, (hipStream_t)stream);
+}
+
+int gs_forward_bounded(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                       const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities,
+                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, int prefiltered, int* radii_out, void* geom_buffer, long long capacity,
+                       void* binning_buffer, void* image_buffer, float* out_color, int debug, void* stream) {
+  return forward_view(
+      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered),
+      FwdOut{radii_out, geom_buffer, capacity, binning_buffer, image_buffer, out_color}, Totals::Bounded, nullptr,
+      debug, (hipStream_t)stream);
+}
+
+// The eager forward with its count read back at the end (gsrast.h): the ordering stores the totals
+// into the readback slot and flags ERR_CAPACITY against `capacity`; the binning and the render are
+// queued behind it on the stream at once, so the device never waits for the host's round trip.
+int gs_forward_counted(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                       const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities,
+                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, int prefiltered, int* radii_out, void* geom_buffer, long long capacity,
+                       void* binning_buffer, void* image_buffer, float* out_color, long long* num_rendered_host,
+                       int debug, void* stream) {
+  return forward_view(
+      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered),
+      FwdOut{radii_out, geom_buffer, capacity, binning_buffer, image_buffer, out_color}, Totals::Counted,
+      num_rendered_host, debug, (hipStream_t)stream);
 }
 
 // The K views' depth sorts as one set of launches (contiguous geometry buffers); GSRAST_BATCH_VIEWS=0
@@ -568,83 +756,94 @@ static bool batch_views() {
   }();
   return on;
 }
+
+// Fork events, one ring per thread and call site: a captured step may hold several forks
+struct EventRing {
+  hipEvent_t ev[4] = {};
+  unsigned next = 0;
+  hipEvent_t take() {  // the next slot's event (created on first use); null: error set
+    hipEvent_t& e = ev[next++ & 3];
+    if (!e && !check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return nullptr;
+    return e;
+  }
+};
+static hipStream_t view_stream(void* const* vs, int v, hipStream_t st) { return vs && vs[v] ? (hipStream_t)vs[v] : st; }
+// the views' later kernels run on their own streams, behind what `st` holds now
+static void fork_to_view_streams(hipEvent_t fork, hipStream_t st, void* const* view_streams, int K) {
+  check_hip(hipEventRecord(fork, st), "hipEventRecord");
+  for (int v = 0; v < K; v++) {
+    hipStream_t vs = view_stream(view_streams, v, st);
+    if (vs != st) check_hip(hipStreamWaitEvent(vs, fork, 0), "hipStreamWaitEvent");
+  }
+}
+
+// The per-view argument arrays of gs_forward_preprocess_views (K entries each)
+struct ViewsIn {
+  int K;
+  const float* const* background;
+  const int *image_width, *image_height;
+  const float *const *viewmatrix, *const *projmatrix, *const *campos;
+  const float *tan_fovx, *tan_fovy;
+  int prefiltered;
+  int* const* radii_out;
+  void* const* geom_buffer;
+  void* const* view_streams;
+};
+
 // capacity (bounded, gs_forward_preprocess_views_bounded): per-view binning capacities; the counts
 // are not read back (num_rendered_host unused), a view over its capacity leaves the sticky flag
-static int preprocess_views_impl(int K, int P, int D, int M, const float* const* background, const int* image_width,
-                                 const int* image_height, const float* means3D, const float* shs,
-                                 const float* colors_precomp, const float* opacities, const float* scales,
-                                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                                 const float* const* viewmatrix, const float* const* projmatrix,
-                                 const float* const* campos, const float* tan_fovx, const float* tan_fovy,
-                                 int prefiltered, int* const* radii_out, void* const* geom_buffer,
-                                 long long* num_rendered_host, const long long* capacity, int debug, void* stream,
-                                 void* const* view_streams) {
+static int preprocess_views(const GaussianArgs& g, const ViewsIn& in, long long* num_rendered_host,
+                            const long long* capacity, int debug, hipStream_t st) {
+  const int K = in.K, P = g.P;
   clear_error(debug);
   if (K <= 0 || K > FUSED_MAX_VIEWS) return set_error("views: 1 to 8 per call"), 1;
-  if (!background || !image_width || !image_height || !viewmatrix || !projmatrix || !campos || !tan_fovx ||
-      !tan_fovy || !radii_out || !geom_buffer || (!num_rendered_host && !capacity))
+  if (!in.background || !in.image_width || !in.image_height || !in.viewmatrix || !in.projmatrix || !in.campos ||
+      !in.tan_fovx || !in.tan_fovy || !in.radii_out || !in.geom_buffer || (!num_rendered_host && !capacity))
     return set_error("missing per-view argument array"), 1;
-  for (int v = 0; v < K; v++) {
-    if (num_rendered_host) num_rendered_host[v] = 0;
-    if (capacity && (capacity[v] < 0 || capacity[v] > GS_MAX_INSTANCES)) return set_error("capacity out of range"), 1;
-    if (!validate(P, D, M, image_width[v], image_height[v], means3D, shs, colors_precomp, opacities, scales, rotations,
-                  cov3D_precomp, viewmatrix[v], projmatrix[v], campos[v], background[v]))
-      return 1;
-    if (P > 0 && (!radii_out[v] || !geom_buffer[v])) return set_error("missing output pointer"), 1;
-  }
-  if (P == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  GaussianArgs g{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier};
   PreViews pv;
   pv.K = K;
   for (int v = 0; v < K; v++) {
-    pv.c[v] = make_camera(background[v], image_width[v], image_height[v], viewmatrix[v], projmatrix[v], campos[v],
-                          tan_fovx[v], tan_fovy[v], prefiltered);
-    pv.radii[v] = radii_out[v];
-    geom_layout((size_t)P, &pv.geo[v], (char*)geom_buffer[v]);
+    if (num_rendered_host) num_rendered_host[v] = 0;
+    if (capacity && (capacity[v] < 0 || capacity[v] > GS_MAX_INSTANCES)) return set_error("capacity out of range"), 1;
+    pv.c[v] = make_camera(in.background[v], in.image_width[v], in.image_height[v], in.viewmatrix[v], in.projmatrix[v],
+                          in.campos[v], in.tan_fovx[v], in.tan_fovy[v], in.prefiltered);
+    if (!validate(g, pv.c[v])) return 1;
+    if (P > 0 && (!in.radii_out[v] || !in.geom_buffer[v])) return set_error("missing output pointer"), 1;
+    pv.radii[v] = in.radii_out[v];
+    geom_layout((size_t)P, &pv.geo[v], (char*)in.geom_buffer[v]);
   }
+  if (P == 0) return 0;
   // (bounded: no readback slot, the views' flags go to the sticky words)
   ReadbackSlot* rb = capacity ? nullptr : readback_slot();
-  if (!capacity && !rb) return 1;
-  BoundedStatus* bs = capacity ? bounded_status() : nullptr;
-  if (capacity && !bs) return 1;
-  if (bs) {
-    long long inst = 0;
-    if (bounded_status_error(take_bounded_status(bs, &inst), inst)) return 1;  // an earlier bounded forward
-  }
-  // one fork event per thread and slot of a ring: a captured step may hold several forks
-  static thread_local hipEvent_t ev_pre[4] = {};
-  static thread_local unsigned ev_next = 0;
-  hipEvent_t& fork = ev_pre[ev_next++ & 3];
-  if (!fork && !check_hip(hipEventCreateWithFlags(&fork, hipEventDisableTiming), "hipEventCreate")) return 1;
+  BoundedStatus* bs = capacity ? bounded_status_checked() : nullptr;
+  if (capacity ? !bs : !rb) return 1;
+  static thread_local EventRing ring;
+  hipEvent_t fork = ring.take();
+  if (!fork) return 1;
   if (!capacity && check_order_flags(false)) return 1;  // earlier forwards' look-back waits (finished ones)
   uint32_t cap32[FUSED_MAX_VIEWS];
   for (int v = 0; v < K; v++) cap32[v] = capacity ? (uint32_t)capacity[v] : 0xFFFFFFFFu;
   // geometry buffers at one stride (slices of one allocation, as prepare_views makes them): the K
   // orderings run as one set of launches on `stream` (blockIdx.y = view), every view's totals
   // stored by the first histogram launch into readback words [8 v, 8 v + 4)
-  const ptrdiff_t vstride = K > 1 ? (char*)geom_buffer[1] - (char*)geom_buffer[0] : 0;
+  void* const* gb = in.geom_buffer;
+  const ptrdiff_t vstride = K > 1 ? (char*)gb[1] - (char*)gb[0] : 0;
   // (up to GS_BATCH_ORDER_MAX Gaussians: larger sorts fill the GPU on their own, and view by view
   // on the views' streams they overlap the other views' render kernels)
   bool batched = batch_views() && K > 1 && P <= GS_BATCH_ORDER_MAX && vstride >= (ptrdiff_t)gs_geom_buffer_bytes(P) &&
                  vstride % 256 == 0;
-  for (int v = 2; v < K && batched; v++) batched = (char*)geom_buffer[v] == (char*)geom_buffer[0] + v * vstride;
+  for (int v = 2; v < K && batched; v++) batched = (char*)gb[v] == (char*)gb[0] + v * vstride;
   fwd_preprocess_views(g, pv, st);
   if (batched) {
     fwd_order(P, pv.geo[0], st, capacity ? nullptr : rb->dev, capacity ? nullptr : rb->ev[0], cap32,
               capacity ? bs->dev : nullptr, K, (uint64_t)vstride);
     // the views' later kernels run on their streams, after the orderings
-    check_hip(hipEventRecord(fork, st), "hipEventRecord");
-    for (int v = 0; v < K; v++) {
-      hipStream_t vs = view_streams && view_streams[v] ? (hipStream_t)view_streams[v] : st;
-      if (vs != st) check_hip(hipStreamWaitEvent(vs, fork, 0), "hipStreamWaitEvent");
-    }
+    fork_to_view_streams(fork, st, in.view_streams, K);
   } else {
     // each view's ordering on its own stream (view_streams[v], or `stream`), after the preprocess
-    check_hip(hipEventRecord(fork, st), "hipEventRecord");
+    fork_to_view_streams(fork, st, in.view_streams, K);
     for (int v = 0; v < K; v++) {
-      hipStream_t vs = view_streams && view_streams[v] ? (hipStream_t)view_streams[v] : st;
-      if (vs != st) check_hip(hipStreamWaitEvent(vs, fork, 0), "hipStreamWaitEvent");
+      hipStream_t vs = view_stream(in.view_streams, v, st);
       if (capacity)
         fwd_order(P, pv.geo[v], vs, nullptr, nullptr, &cap32[v], bs->dev);
       else
@@ -672,10 +871,12 @@ int gs_forward_preprocess_views(int K, int P, int D, int M, const float* const* 
     clear_error(debug);
     return set_error("missing per-view argument array"), 1;
   }
-  return preprocess_views_impl(K, P, D, M, background, image_width, image_height, means3D, shs, colors_precomp,
-                               opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                               campos, tan_fovx, tan_fovy, prefiltered, radii_out, geom_buffer, num_rendered_host,
-                               nullptr, debug, stream, view_streams);
+  return preprocess_views(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      ViewsIn{K, background, image_width, image_height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+              prefiltered, radii_out, geom_buffer, view_streams},
+      num_rendered_host, nullptr, debug, (hipStream_t)stream);
 }
 
 int gs_forward_preprocess_views_bounded(int K, int P, int D, int M, const float* const* background,
@@ -691,48 +892,12 @@ int gs_forward_preprocess_views_bounded(int K, int P, int D, int M, const float*
     clear_error(debug);
     return set_error("missing capacity array"), 1;
   }
-  return preprocess_views_impl(K, P, D, M, background, image_width, image_height, means3D, shs, colors_precomp,
-                               opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                               campos, tan_fovx, tan_fovy, prefiltered, radii_out, geom_buffer, nullptr, capacity,
-                               debug, stream, view_streams);
-}
-
-static int forward_render_impl(int P, const float* background, int W, int H, const float* viewmatrix,
-                               const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                               const int* radii, void* geom_buffer, long long num_rendered, void* binning_buffer,
-                               void* image_buffer, float* out_color, bool bounded, int debug, void* stream,
-                               unsigned long long* oseq_out = nullptr, const FwdAux& aux = FwdAux()) {
-  clear_error(debug);
-  if (P <= 0) return 0;
-  if (W <= 0 || H <= 0) return set_error("image size must be positive"), 1;
-  if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
-  if (!geom_buffer || !binning_buffer || !image_buffer || !out_color || !radii)
-    return set_error("missing buffer pointer"), 1;
-  hipStream_t st = (hipStream_t)stream;
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
-  GeomPtrs geo;
-  BinPtrs bin;
-  ImgPtrs img;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  bin_layout((size_t)num_rendered, c.gx * c.gy, &bin, (char*)binning_buffer);
-  img_layout(W, H, &img, (char*)image_buffer);
-  // the look-back waits of the offsets scan and of the one-sweep sorts (never expected to run out:
-  // the waited-for workgroups are running) leave ERR_LOOKBACK; the render kernel stores the flags
-  // into pinned memory, behind an event that the next backward or forward call checks, so no host
-  // wait idles the device
-  // (bounded: the sticky word, nothing recorded or checked here)
-  BoundedStatus* bs = bounded ? bounded_status() : nullptr;
-  unsigned long long oseq = 0;
-  uint32_t* flags_word = bounded ? (bs ? bs->dev + 4 : nullptr) : order_flags_word(&oseq);
-  if (!flags_word) return 1;
-  fwd_bin(P, (uint32_t)num_rendered, c, radii, geo, bin, img, st);
-  fwd_render(c, geo, bin, img, out_color, st, flags_word, aux);
-  if (!bounded) {
-    if (oseq_out) *oseq_out = oseq;
-    if (t_failed) release_order_word(oseq);
-    else if (queue_order_flags(st, oseq)) return 1;
-  }
-  return t_failed ? 1 : 0;
+  return preprocess_views(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      ViewsIn{K, background, image_width, image_height, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+              prefiltered, radii_out, geom_buffer, view_streams},
+      nullptr, capacity, debug, (hipStream_t)stream);
 }
 
 int gs_forward_bin_views(int K, int P, int W, int H, void* const* geom_buffer, const long long* num_rendered,
@@ -751,7 +916,7 @@ int gs_forward_bin_views(int K, int P, int W, int H, void* const* geom_buffer, c
     I = num_rendered[v] > I ? num_rendered[v] : I;
   }
   hipStream_t st = (hipStream_t)stream;
-  CameraArgs c = make_camera(nullptr, W, H, nullptr, nullptr, nullptr, 1.0f, 1.0f, 0);
+  const CameraArgs c = size_camera(W, H);
   // every view's buffers at one stride per kind (slices of one allocation each)
   auto stride_of = [&](void* const* b, size_t min_bytes, uint64_t* out) {
     const ptrdiff_t d = K > 1 ? (char*)b[1] - (char*)b[0] : 0;
@@ -767,188 +932,23 @@ int gs_forward_bin_views(int K, int P, int W, int H, void* const* geom_buffer, c
       !stride_of(image_buffer, gs_image_buffer_bytes(W, H), &is))
     return set_error("bin_views: each kind of buffer must be K slices of one allocation, one stride apart, each "
                      "sized for the largest num_rendered"), 1;
-  GeomPtrs geo;
-  BinPtrs bin;
-  ImgPtrs img;
   if (!batch_views() || I > (long long)GS_BATCH_BIN_MAX) {
     // large views: each view's binning on its own stream, where it overlaps the other views'
     // render kernels (a batched sort of K large views would serialise in front of them)
     for (int v = 0; v < K; v++) {
-      hipStream_t vs = view_streams && view_streams[v] ? (hipStream_t)view_streams[v] : st;
-      geom_layout((size_t)P, &geo, (char*)geom_buffer[v]);
-      bin_layout((size_t)I, c.gx * c.gy, &bin, (char*)binning_buffer[v]);
-      img_layout(W, H, &img, (char*)image_buffer[v]);
-      fwd_bin_views(1, P, (uint32_t)I, c, geo, bin, img, 0, 0, 0, vs);
+      const Layouts L(P, I, c, geom_buffer[v], binning_buffer[v], image_buffer[v]);
+      fwd_bin_views(1, P, (uint32_t)I, c, L.geo, L.bin, L.img, 0, 0, 0, view_stream(view_streams, v, st));
     }
     return t_failed ? 1 : 0;
   }
-  geom_layout((size_t)P, &geo, (char*)geom_buffer[0]);
-  bin_layout((size_t)I, c.gx * c.gy, &bin, (char*)binning_buffer[0]);
-  img_layout(W, H, &img, (char*)image_buffer[0]);
-  fwd_bin_views(K, P, (uint32_t)I, c, geo, bin, img, gs, bs, is, st);
+  const Layouts L(P, I, c, geom_buffer[0], binning_buffer[0], image_buffer[0]);
+  fwd_bin_views(K, P, (uint32_t)I, c, L.geo, L.bin, L.img, gs, bs, is, st);
   // the views' renders run on their streams, after the binning
-  static thread_local hipEvent_t ev_bin[4] = {};
-  static thread_local unsigned ev_next = 0;
-  hipEvent_t& done = ev_bin[ev_next++ & 3];
-  if (!done && !check_hip(hipEventCreateWithFlags(&done, hipEventDisableTiming), "hipEventCreate")) return 1;
-  check_hip(hipEventRecord(done, st), "hipEventRecord");
-  for (int v = 0; v < K; v++) {
-    hipStream_t vs = view_streams && view_streams[v] ? (hipStream_t)view_streams[v] : st;
-    if (vs != st) check_hip(hipStreamWaitEvent(vs, done, 0), "hipStreamWaitEvent");
-  }
+  static thread_local EventRing ring;
+  hipEvent_t done = ring.take();
+  if (!done) return 1;
+  fork_to_view_streams(done, st, view_streams, K);
   return t_failed ? 1 : 0;
-}
-
-int gs_forward_render_binned(int P, const float* background, int W, int H, const float* viewmatrix,
-                             const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                             void* geom_buffer, long long num_rendered, void* binning_buffer, void* image_buffer,
-                             float* out_color, int bounded, int debug, void* stream) {
-  clear_error(debug);
-  if (P <= 0) return 0;
-  if (W <= 0 || H <= 0) return set_error("image size must be positive"), 1;
-  if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
-  if (!geom_buffer || !binning_buffer || !image_buffer || !out_color) return set_error("missing buffer pointer"), 1;
-  hipStream_t st = (hipStream_t)stream;
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
-  GeomPtrs geo;
-  BinPtrs bin;
-  ImgPtrs img;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  bin_layout((size_t)num_rendered, c.gx * c.gy, &bin, (char*)binning_buffer);
-  img_layout(W, H, &img, (char*)image_buffer);
-  BoundedStatus* bst = bounded ? bounded_status() : nullptr;
-  unsigned long long oseq = 0;
-  uint32_t* flags_word = bounded ? (bst ? bst->dev + 4 : nullptr) : order_flags_word(&oseq);
-  if (!flags_word) return 1;
-  fwd_render(c, geo, bin, img, out_color, st, flags_word);
-  if (!bounded) {
-    if (t_failed) release_order_word(oseq);
-    else if (queue_order_flags(st, oseq)) return 1;
-  }
-  return t_failed ? 1 : 0;
-}
-
-int gs_forward_render(int P, const float* background, int W, int H, const float* viewmatrix, const float* projmatrix,
-                      const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                      long long num_rendered, void* binning_buffer, void* image_buffer, float* out_color, int debug,
-                      void* stream) {
-  return forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                             geom_buffer, num_rendered, binning_buffer, image_buffer, out_color, false, debug, stream);
-}
-
-int gs_forward_render_aux(int P, const float* background, int W, int H, const float* viewmatrix,
-                          const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                          const int* radii, void* geom_buffer, long long num_rendered, void* binning_buffer,
-                          void* image_buffer, float* out_color, float* out_invdepth, float* out_alpha, int debug,
-                          void* stream) {
-  FwdAux aux;
-  aux.invdepth = out_invdepth;
-  aux.alpha = out_alpha;
-  return forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                             geom_buffer, num_rendered, binning_buffer, image_buffer, out_color, false, debug, stream,
-                             nullptr, aux);
-}
-
-int gs_forward_render_bounded(int P, const float* background, int W, int H, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, void* geom_buffer, long long capacity, void* binning_buffer,
-                              void* image_buffer, float* out_color, int debug, void* stream) {
-  return forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                             geom_buffer, capacity, binning_buffer, image_buffer, out_color, true, debug, stream);
-}
-
-int gs_forward_bounded(int P, int D, int M, const float* background, int W, int H, const float* means3D,
-                       const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities,
-                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                       float tan_fovy, int prefiltered, int* radii_out, void* geom_buffer, long long capacity,
-                       void* binning_buffer, void* image_buffer, float* out_color, int debug, void* stream) {
-  clear_error(debug);
-  if (!validate(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
-                projmatrix, campos, background))
-    return 1;
-  if (!validate_split(M, shs, shs_rest, colors_precomp)) return 1;
-  if (P == 0) return 0;
-  if (capacity < 0 || capacity > GS_MAX_INSTANCES) return set_error("capacity out of range"), 1;
-  if (!radii_out || !geom_buffer || !binning_buffer || !image_buffer || !out_color)
-    return set_error("missing buffer pointer"), 1;
-  BoundedStatus* bs = bounded_status();
-  if (!bs) return 1;
-  long long inst = 0;
-  if (bounded_status_error(take_bounded_status(bs, &inst), inst)) return 1;  // an earlier bounded forward
-  hipStream_t st = (hipStream_t)stream;
-  GeomPtrs geo;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  GaussianArgs g{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier,
-                 shs_rest};
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered);
-  fwd_preprocess(g, c, radii_out, geo, st);
-  const uint32_t cap32 = (uint32_t)capacity;
-  fwd_order(P, geo, st, nullptr, nullptr, &cap32, bs->dev);
-  if (t_failed) return 1;
-  return forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii_out,
-                             geom_buffer, capacity, binning_buffer, image_buffer, out_color, true, debug, stream);
-}
-
-// The eager forward with its count read back at the end (gsrast.h): the ordering stores the totals
-// into the readback slot and flags ERR_CAPACITY against `capacity`; the binning and the render are
-// queued behind it on the stream at once, so the device never waits for the host's round trip.
-int gs_forward_counted(int P, int D, int M, const float* background, int W, int H, const float* means3D,
-                       const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities,
-                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                       float tan_fovy, int prefiltered, int* radii_out, void* geom_buffer, long long capacity,
-                       void* binning_buffer, void* image_buffer, float* out_color, long long* num_rendered_host,
-                       int debug, void* stream) {
-  clear_error(debug);
-  if (num_rendered_host) *num_rendered_host = 0;
-  if (!validate(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
-                projmatrix, campos, background))
-    return 1;
-  if (!validate_split(M, shs, shs_rest, colors_precomp)) return 1;
-  if (P == 0) return 0;
-  if (capacity < 0 || capacity > GS_MAX_INSTANCES) return set_error("capacity out of range"), 1;
-  if (!radii_out || !geom_buffer || !binning_buffer || !image_buffer || !out_color || !num_rendered_host)
-    return set_error("missing buffer pointer"), 1;
-  ReadbackSlot* rb = readback_slot();
-  if (!rb) return 1;
-  if (check_order_flags(false)) return 1;  // earlier forwards' look-back waits (the finished ones)
-  hipStream_t st = (hipStream_t)stream;
-  GeomPtrs geo;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  GaussianArgs g{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier,
-                 shs_rest};
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered);
-  fwd_preprocess(g, c, radii_out, geo, st);
-  const uint32_t cap32 = (uint32_t)capacity;
-  fwd_order(P, geo, st, rb->dev, rb->ev[0], &cap32, nullptr);
-  // the count readback is queued into this thread's slot: every return from here on waits for it,
-  // so no kernel of this call can still write the slot's words when the thread's next call reads them
-  auto drain = [&]() { (void)hipEventSynchronize(rb->ev[0]); };
-  if (t_failed) return drain(), 1;
-  unsigned long long oseq = 0;
-  if (forward_render_impl(P, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii_out,
-                          geom_buffer, capacity, binning_buffer, image_buffer, out_color, false, debug, stream,
-                          &oseq))
-    return drain(), 1;
-  check_hip(hipEventSynchronize(rb->ev[0]), "hipEventSynchronize");
-  if (t_failed) return 1;
-  // (this forward's render is queued: check the others, without waiting for it)
-  if (check_order_flags(true, (long long)oseq)) return 1;
-  long long I = 0;
-  if (!read_view_totals(rb->host, 0, 1, &I)) return 1;
-  *num_rendered_host = I;
-  if (I > capacity) {
-    // the queued binning and render skipped their work (ERR_CAPACITY): clear the flag so that
-    // gs_forward_render can bin the same geometry into a buffer of the exact size
-    fwd_clear_flags(geo, ERR_CAPACITY, st);
-    // the skipped render carries this ordering's look-back flags: read them now (it finishes
-    // quickly, having skipped its work), so a timed-out ordering fails here, once, instead of
-    // again at the next call through the re-binned forward's flags
-    if (t_failed || check_order_seq(oseq)) return 1;
-    return GS_COUNT_SHORT;
-  }
-  return 0;
 }
 
 int gs_bounded_status(unsigned* flags, long long* instances) {
@@ -1018,61 +1018,56 @@ long long gs_rasterize_forward(int P, int D, int M, const float* background, int
   return I;
 }
 
-static int backward_impl(int P, int D, int M, const float* background, int W, int H, const float* means3D,
-                         const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities, const float* scales,
-                         float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                         const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                         float tan_fovy, const void* geom_buffer, long long num_rendered, const void* binning_buffer,
-                         const void* image_buffer, const float* dL_dout_color, void* grad_buffer, float* dL_dmeans2D,
-                         float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscales, float* dL_drotations, unsigned accumulate, void* wait_event, int debug,
-                         void* stream, const float* dL_dout_invdepth = nullptr,
-                         const float* dL_dout_alpha = nullptr) {
+// ---- backward: the same packing (make_scene, make_camera, BwdIn, GradOut) ----
+// What a view's backward reads besides the scene, and its scratch
+struct BwdIn {
+  const void* geom;
+  long long num_rendered;
+  const void* binning;
+  const void* image;
+  const float* dL_dout_color;
+  void* grad_buffer;
+  const float* dL_dout_invdepth = nullptr;  // gs_backward_accumulate_aux (either may be null)
+  const float* dL_dout_alpha = nullptr;
+};
+
+// out: the caller's gradient pointers as passed; the ones the scene's inputs cannot receive are dropped here
+static int backward_impl(const GaussianArgs& g, const CameraArgs& c, const BwdIn& in, GradOut out, void* wait_event,
+                         int debug, hipStream_t st) {
+  const int P = g.P;
+  const long long num_rendered = in.num_rendered;
   clear_error(debug);
-  (void)opacities;  // the opacity is carried by the forward's splat records
-  if (!validate(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
-                projmatrix, campos, background, false))
-    return 1;
-  if (!validate_split(M, shs, shs_rest, colors_precomp)) return 1;
+  // (the opacity is carried by the forward's splat records: not required here)
+  if (!validate(g, c, false)) return 1;
   if (P == 0) return 0;
-  if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dout_color || !grad_buffer)
+  if (!in.geom || !in.binning || !in.image || !in.dL_dout_color || !in.grad_buffer)
     return set_error("missing buffer pointer"), 1;
-  if (!dL_dmeans2D || !dL_dopacity || !dL_dmeans3D) return set_error("missing gradient output pointer"), 1;
+  if (!out.dmean2D || !out.dopacity || !out.dmean3D) return set_error("missing gradient output pointer"), 1;
   if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
-  if (accumulate & ~0xFFu) return set_error("accumulate: unknown GS_ACC bits 0x%x", accumulate), 1;
-  hipStream_t st = (hipStream_t)stream;
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
-  GeomPtrs geo;
-  BinPtrs bin;
-  ImgPtrs img;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  bin_layout((size_t)num_rendered, c.gx * c.gy, &bin, (char*)binning_buffer);
-  img_layout(W, H, &img, (char*)image_buffer);
-  GaussianArgs g{P, D, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier,
-                 shs_rest};
-  float* gradrec = (float*)grad_buffer;
+  if (out.acc & ~0xFFu) return set_error("accumulate: unknown GS_ACC bits 0x%x", out.acc), 1;
+  const Layouts L(P, num_rendered, c, in.geom, in.binning, in.image);
+  float* gradrec = (float*)in.grad_buffer;
   // an aux gradient (gs_backward_accumulate_aux): the side arrays behind the records; none: the plain path
   BwdAux aux;
-  if (dL_dout_invdepth || dL_dout_alpha) {
+  if (in.dL_dout_invdepth || in.dL_dout_alpha) {
     size_t o_rec = 0, o_sum = 0;
     grad_layout_aux((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)P, &o_rec, &o_sum);
-    aux.d_invdepth = dL_dout_invdepth;
-    aux.d_alpha = dL_dout_alpha;
-    aux.gradrec_aux = (float*)((char*)grad_buffer + o_rec);
-    aux.gsum_aux = (float*)((char*)grad_buffer + o_sum);
+    aux.d_invdepth = in.dL_dout_invdepth;
+    aux.d_alpha = in.dL_dout_alpha;
+    aux.gradrec_aux = (float*)((char*)in.grad_buffer + o_rec);
+    aux.gsum_aux = (float*)((char*)in.grad_buffer + o_sum);
   }
-  if (num_rendered > 0) bwd_render(P, c, geo, bin, img, dL_dout_color, gradrec, st, aux);
+  if (num_rendered > 0) bwd_render(P, c, L.geo, L.bin, L.img, in.dL_dout_color, gradrec, st, aux);
   // dL_dcov3D is filled whenever the caller passes it: upstream writes it for scale/rotation
   // inputs too (the covariance gradient the scale / rotation chain starts from)
-  GradOut out{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
-              shs ? dL_dsh : nullptr, cov3D_precomp ? nullptr : dL_dscales, cov3D_precomp ? nullptr : dL_drotations,
-              accumulate};
+  if (!g.shs) out.dsh = nullptr;
+  if (g.cov3D) out.dscale = out.drot = nullptr;
   // the gradient outputs may be shared with views on other streams: order only this last kernel
   if (wait_event && !check_hip(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0), "hipStreamWaitEvent")) return 1;
-  bwd_preprocess(g, c, geo, bin, img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st, aux);
+  bwd_preprocess(g, c, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st, aux);
   if (aux.on() && num_rendered > 0) {
     // the depth chain's term, added after the kernel that wrote dL_dmeans3D (same stream, behind the wait)
-    bwd_depth_chain(g, c, geo, aux, dL_dmeans3D, st);
+    bwd_depth_chain(g, c, L.geo, aux, out.dmean3D, st);
   }
   // the ordering flags of the forwards that have finished, now that this backward's kernels are queued
   if (!t_failed && check_order_flags(false)) return 1;
@@ -1087,12 +1082,11 @@ int gs_backward(int P, int D, int M, const float* background, int W, int H, cons
                 const float* dL_dout_color, void* grad_buffer, float* dL_dmeans2D, float* dL_dcolors,
                 float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                 float* dL_drotations, int debug, void* stream) {
-  (void)radii;
-  return backward_impl(P, D, M, background, W, H, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier,
-                       rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer,
-                       num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dmeans2D,
-                       dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, 0u, nullptr,
-                       debug, stream);
+  return gs_backward_accumulate(P, D, M, background, W, H, means3D, shs, colors_precomp, opacities, scales,
+                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                                tan_fovy, radii, geom_buffer, num_rendered, binning_buffer, image_buffer,
+                                dL_dout_color, grad_buffer, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
+                                dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, 0u, nullptr, debug, stream);
 }
 
 int gs_backward_accumulate(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1106,11 +1100,14 @@ int gs_backward_accumulate(int P, int D, int M, const float* background, int W, 
                            float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                            unsigned accumulate, void* wait_event, int debug, void* stream) {
   (void)radii;
-  return backward_impl(P, D, M, background, W, H, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier,
-                       rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer,
-                       num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dmeans2D,
-                       dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, accumulate,
-                       wait_event, debug, stream);
+  return backward_impl(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+      BwdIn{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer},
+      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+              accumulate},
+      wait_event, debug, (hipStream_t)stream);
 }
 
 int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1125,11 +1122,15 @@ int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int
                                float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                                unsigned accumulate, void* wait_event, int debug, void* stream) {
   (void)radii;
-  return backward_impl(P, D, M, background, W, H, means3D, shs, shs_rest, colors_precomp, opacities, scales,
-                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                       geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer,
-                       dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                       dL_drotations, accumulate, wait_event, debug, stream, dL_dout_invdepth, dL_dout_alpha);
+  return backward_impl(
+      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+      BwdIn{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dout_invdepth,
+            dL_dout_alpha},
+      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+              accumulate},
+      wait_event, debug, (hipStream_t)stream);
 }
 
 int gs_backward_accumulate_split(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1147,11 +1148,14 @@ int gs_backward_accumulate_split(int P, int D, int M, const float* background, i
     clear_error(debug);
     return set_error("split SH: features_rest is NULL"), 1;
   }
-  return backward_impl(P, D, M, background, W, H, means3D, shs_dc, shs_rest, nullptr, opacities, scales,
-                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                       geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer,
-                       dL_dmeans2D, nullptr, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-                       accumulate, wait_event, debug, stream);
+  return backward_impl(
+      make_scene(P, D, M, means3D, shs_dc, shs_rest, nullptr, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
+      BwdIn{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer},
+      GradOut{dL_dmeans2D, nullptr, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+              accumulate},
+      wait_event, debug, (hipStream_t)stream);
 }
 
 int gs_backward_render(int P, int D, int M, const float* background, int W, int H, const float* viewmatrix,
@@ -1159,6 +1163,7 @@ int gs_backward_render(int P, int D, int M, const float* background, int W, int 
                        const void* geom_buffer, long long num_rendered, const void* binning_buffer,
                        const void* image_buffer, const float* dL_dout_color, void* grad_buffer, float* dL_dmeans2D,
                        unsigned accumulate, int debug, void* stream) {
+  const CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
   clear_error(debug);
   if (P < 0) return set_error("P must be >= 0"), 1;
   if (W <= 0 || H <= 0) return set_error("image size must be positive (got %d x %d)", W, H), 1;
@@ -1169,57 +1174,52 @@ int gs_backward_render(int P, int D, int M, const float* background, int W, int 
   if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
   if (accumulate & ~GS_ACC_MEANS2D) return set_error("accumulate: only GS_ACC_MEANS2D applies here"), 1;
   hipStream_t st = (hipStream_t)stream;
-  CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
-  GeomPtrs geo;
-  BinPtrs bin;
-  ImgPtrs img;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  bin_layout((size_t)num_rendered, c.gx * c.gy, &bin, (char*)binning_buffer);
-  img_layout(W, H, &img, (char*)image_buffer);
-  GaussianArgs g{P, D, M, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f};
+  const Layouts L(P, num_rendered, c, geom_buffer, binning_buffer, image_buffer);
+  // (the record sums read the scene's sizes only)
+  const GaussianArgs g = make_scene(P, D, M, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, nullptr,
+                                    nullptr);
   float* gradrec = (float*)grad_buffer;
-  if (num_rendered > 0) bwd_render(P, c, geo, bin, img, dL_dout_color, gradrec, st);
-  bwd_records(g, geo, bin, img, gradrec, (uint32_t)num_rendered, num_rendered > 0, dL_dmeans2D, accumulate, st);
+  if (num_rendered > 0) bwd_render(P, c, L.geo, L.bin, L.img, dL_dout_color, gradrec, st);
+  bwd_records(g, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, dL_dmeans2D, accumulate, st);
   if (!t_failed && check_order_flags(false)) return 1;
   return t_failed ? 1 : 0;
 }
 
-static int backward_gaussians_impl(int P, int first, int count, int D, int M, const float* means3D, const float* shs,
-                                   const float* colors_precomp, const float* scales, float scale_modifier,
-                                   const float* rotations, const float* cov3D_precomp, int num_views,
-                                   const gs_view_grad* views, float* dL_dcolors, float* dL_dopacity,
-                                   float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                                   float* dL_drotations, unsigned accumulate, void* wait_event, int debug,
-                                   void* stream) {
+// scene, grads: the whole scene and the caller's gradient pointers (P rows), of which [first, first + count) run
+static int backward_gaussians_impl(const GaussianArgs& scene, int first, int count, int num_views,
+                                   const gs_view_grad* views, const GradOut& grads, void* wait_event, int debug,
+                                   hipStream_t st) {
+  const int P = scene.P;
   clear_error(debug);
   if (P < 0) return set_error("P must be >= 0"), 1;
   if (first < 0 || count < 0 || (long long)first + count > P) return set_error("Gaussian range out of bounds"), 1;
   if (num_views < 0 || (num_views > 0 && !views)) return set_error("bad view list"), 1;
   if (P == 0 || count == 0 || num_views == 0) return 0;
-  if (!means3D) return set_error("missing required input pointer"), 1;
-  if ((shs == nullptr) == (colors_precomp == nullptr))
+  if (!scene.means3D) return set_error("missing required input pointer"), 1;
+  if ((scene.shs == nullptr) == (scene.colors == nullptr))
     return set_error("Please provide excatly one of either SHs or precomputed colors!"), 1;
-  if (((scales == nullptr || rotations == nullptr) && cov3D_precomp == nullptr) ||
-      ((scales || rotations) && cov3D_precomp))
+  if (((scene.scales == nullptr || scene.rotations == nullptr) && scene.cov3D == nullptr) ||
+      ((scene.scales || scene.rotations) && scene.cov3D))
     return set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!"), 1;
-  if (shs && (D < 0 || D > 3 || M < (D + 1) * (D + 1))) return set_error("bad SH degree / coefficient count"), 1;
-  if (!dL_dopacity || !dL_dmeans3D) return set_error("missing gradient output pointer"), 1;
-  if (accumulate & ~0xFFu) return set_error("accumulate: unknown GS_ACC bits 0x%x", accumulate), 1;
+  if (scene.shs && (scene.D < 0 || scene.D > 3 || scene.M < (scene.D + 1) * (scene.D + 1)))
+    return set_error("bad SH degree / coefficient count"), 1;
+  if (!grads.dopacity || !grads.dmean3D) return set_error("missing gradient output pointer"), 1;
+  if (grads.acc & ~0xFFu) return set_error("accumulate: unknown GS_ACC bits 0x%x", grads.acc), 1;
   for (int v = 0; v < num_views; v++) {
     const gs_view_grad& w = views[v];
-    if (!w.viewmatrix || !w.projmatrix || !w.geom_buffer || (shs && !w.campos))
+    if (!w.viewmatrix || !w.projmatrix || !w.geom_buffer || (scene.shs && !w.campos))
       return set_error("view %d: missing pointer", v), 1;
     if (w.image_width <= 0 || w.image_height <= 0) return set_error("view %d: bad image size", v), 1;
   }
-  hipStream_t st = (hipStream_t)stream;
   if (wait_event && !check_hip(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0), "hipStreamWaitEvent")) return 1;
   // the range [first, first + count) as a P = count problem: every per-Gaussian array is row-indexed,
   // so the rows' pointers are offset by `first` (the geom buffers keep their P-row layout)
-  const size_t f = (size_t)first;
+  const size_t f = (size_t)first, M = (size_t)scene.M;
   auto off = [f](const float* p, size_t w) { return p ? p + f * w : nullptr; };
   auto offw = [f](float* p, size_t w) { return p ? p + f * w : nullptr; };
-  GaussianArgs g{count, D, M, off(means3D, 3), off(shs, 3 * (size_t)M), off(colors_precomp, 3), nullptr,
-                 off(scales, 3), off(rotations, 4), off(cov3D_precomp, 6), scale_modifier};
+  const GaussianArgs g = make_scene(count, scene.D, scene.M, off(scene.means3D, 3), off(scene.shs, 3 * M), nullptr,
+                                    off(scene.colors, 3), nullptr, off(scene.scales, 3), scene.scale_modifier,
+                                    off(scene.rotations, 4), off(scene.cov3D, 6));
   // passes of up to FUSED_MAX_VIEWS views; the later passes add to what the earlier wrote
   for (int v0 = 0; v0 < num_views; v0 += FUSED_MAX_VIEWS) {
     FusedViews fv;
@@ -1234,9 +1234,10 @@ static int backward_gaussians_impl(int P, int first, int count, int D, int M, co
       fv.v[k].clamped = geo.clamped + f;
       fv.v[k].gsum = geo.gsum + f * GRAD_REC;
     }
-    GradOut out{nullptr, offw(dL_dcolors, 3), offw(dL_dopacity, 1), offw(dL_dmeans3D, 3), offw(dL_dcov3D, 6),
-                shs ? offw(dL_dsh, 3 * (size_t)M) : nullptr, cov3D_precomp ? nullptr : offw(dL_dscales, 3),
-                cov3D_precomp ? nullptr : offw(dL_drotations, 4), v0 == 0 ? accumulate : 0xFFu};
+    const GradOut out{nullptr, offw(grads.dcolor, 3), offw(grads.dopacity, 1), offw(grads.dmean3D, 3),
+                      offw(grads.dcov3D, 6), scene.shs ? offw(grads.dsh, 3 * M) : nullptr,
+                      scene.cov3D ? nullptr : offw(grads.dscale, 3), scene.cov3D ? nullptr : offw(grads.drot, 4),
+                      v0 == 0 ? grads.acc : 0xFFu};
     bwd_gaussians(g, fv, out, st);
   }
   return t_failed ? 1 : 0;
@@ -1248,9 +1249,9 @@ int gs_backward_gaussians(int P, int D, int M, const float* means3D, const float
                           float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                           float* dL_dscales, float* dL_drotations, unsigned accumulate, void* wait_event, int debug,
                           void* stream) {
-  return backward_gaussians_impl(P, 0, P, D, M, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                                 cov3D_precomp, num_views, views, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
-                                 dL_dsh, dL_dscales, dL_drotations, accumulate, wait_event, debug, stream);
+  return gs_backward_gaussians_range(P, 0, P, D, M, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
+                                     cov3D_precomp, num_views, views, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
+                                     dL_dsh, dL_dscales, dL_drotations, accumulate, wait_event, debug, stream);
 }
 
 int gs_backward_gaussians_range(int P, int first, int count, int D, int M, const float* means3D, const float* shs,
@@ -1259,9 +1260,12 @@ int gs_backward_gaussians_range(int P, int first, int count, int D, int M, const
                                 const gs_view_grad* views, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                                 float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                                 unsigned accumulate, void* wait_event, int debug, void* stream) {
-  return backward_gaussians_impl(P, first, count, D, M, means3D, shs, colors_precomp, scales, scale_modifier,
-                                 rotations, cov3D_precomp, num_views, views, dL_dcolors, dL_dopacity, dL_dmeans3D,
-                                 dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, accumulate, wait_event, debug, stream);
+  return backward_gaussians_impl(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, nullptr, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      first, count, num_views, views,
+      GradOut{nullptr, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, accumulate},
+      wait_event, debug, (hipStream_t)stream);
 }
 
 int gs_backward_gaussians_adam(int P, int D, int M, const float* means3D, const float* shs_dc, const float* shs_rest,
@@ -1300,9 +1304,9 @@ int gs_backward_gaussians_adam_stats(int P, int D, int M, const float* means3D, 
   }
   if (means3D != params_host[DT_XYZ]) return set_error("means3D must be the xyz parameter (params_host[0])"), 1;
   if (((uintptr_t)params_host[DT_ROT]) & 15) return set_error("rotation parameter must be 16-byte aligned"), 1;
-  GaussianArgs g{P, D, M, means3D, shs_dc, nullptr, nullptr, scales, rotations, nullptr, scale_modifier};
-  g.shs_rest = shs_rest;
   if ((((uintptr_t)shs_dc) | ((uintptr_t)shs_rest)) & 15) return set_error("split SH rows must be 16-byte aligned"), 1;
+  const GaussianArgs g = make_scene(P, D, M, means3D, shs_dc, shs_rest, nullptr, nullptr, scales, scale_modifier,
+                                    rotations, nullptr);
   FusedAdamArgs a{};
   for (int k = 0; k < 6; k++) {
     a.p[k] = params_host[k];
@@ -1323,8 +1327,8 @@ int gs_backward_gaussians_adam_stats(int P, int D, int M, const float* means3D, 
   GeomPtrs geo;
   geom_layout((size_t)P, &geo, (char*)view->geom_buffer);
   a.err = &geo.counters[CNT_ERR];
-  CameraArgs c = make_camera(nullptr, view->image_width, view->image_height, view->viewmatrix, view->projmatrix,
-                             view->campos, view->tan_fovx, view->tan_fovy, 0);
+  const CameraArgs c = make_camera(nullptr, view->image_width, view->image_height, view->viewmatrix, view->projmatrix,
+                                   view->campos, view->tan_fovx, view->tan_fovy, 0);
   bwd_gaussians_adam(g, c, geo, a, (hipStream_t)stream);
   return t_failed ? 1 : 0;
 }
@@ -1642,26 +1646,22 @@ int gs_debug_export(int P, int W, int H, long long num_rendered, const void* geo
   hipStream_t st = (hipStream_t)stream;
   const int gx = (W + GS_TILE - 1) / GS_TILE, gy = (H + GS_TILE - 1) / GS_TILE;
   if (P <= 0) return 0;
-  GeomPtrs geo;
-  BinPtrs bin;
-  ImgPtrs img;
-  geom_layout((size_t)P, &geo, (char*)geom_buffer);
-  bin_layout((size_t)num_rendered, gx * gy, &bin, (char*)binning_buffer);
-  img_layout(W, H, &img, (char*)image_buffer);
+  const Layouts L(P, num_rendered, size_camera(W, H), geom_buffer, binning_buffer, image_buffer);
   if (point_list && num_rendered > 0)
     GS_LAUNCH("export_list", k_export_list, dim3((unsigned)((num_rendered + 255) / 256)), dim3(256), 0, st,
-              (uint32_t)num_rendered, geo.counters, bin.point_list, bin.presort_gid,
-              point_list);
-  if (ranges) check_hip(hipMemcpyAsync(ranges, img.ranges, sizeof(uint2) * gx * gy, hipMemcpyDeviceToDevice, st), "copy");
+              (uint32_t)num_rendered, L.geo.counters, L.bin.point_list, L.bin.presort_gid, point_list);
+  if (ranges)
+    check_hip(hipMemcpyAsync(ranges, L.img.ranges, sizeof(uint2) * gx * gy, hipMemcpyDeviceToDevice, st), "copy");
   if (xy || conic_opacity || rgb || depth)
-    GS_LAUNCH("export_splat", k_export_splat, dim3((P + 255) / 256), dim3(256), 0, st, P, geo.splat, xy, conic_opacity,
-              rgb, depth);
+    GS_LAUNCH("export_splat", k_export_splat, dim3((P + 255) / 256), dim3(256), 0, st, P, L.geo.splat, xy,
+              conic_opacity, rgb, depth);
   if (tiles_touched)
-    check_hip(hipMemcpyAsync(tiles_touched, geo.tiles, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, st), "copy");
+    check_hip(hipMemcpyAsync(tiles_touched, L.geo.tiles, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, st), "copy");
   if (final_T)
-    check_hip(hipMemcpyAsync(final_T, img.final_T, sizeof(float) * W * H, hipMemcpyDeviceToDevice, st), "copy");
+    check_hip(hipMemcpyAsync(final_T, L.img.final_T, sizeof(float) * W * H, hipMemcpyDeviceToDevice, st), "copy");
   if (n_contrib)
-    check_hip(hipMemcpyAsync(n_contrib, img.n_contrib, sizeof(uint32_t) * W * H, hipMemcpyDeviceToDevice, st), "copy");
+    check_hip(hipMemcpyAsync(n_contrib, L.img.n_contrib, sizeof(uint32_t) * W * H, hipMemcpyDeviceToDevice, st),
+              "copy");
   return t_failed ? 1 : 0;
 }
 
@@ -1671,16 +1671,13 @@ int gs_debug_export_slots(int W, int H, long long num_rendered, const void* binn
   hipStream_t st = (hipStream_t)stream;
   if (W <= 0 || H <= 0 || num_rendered < 0) return set_error("debug_export_slots: bad arguments"), 1;
   const int gx = (W + GS_TILE - 1) / GS_TILE, gy = (H + GS_TILE - 1) / GS_TILE;
-  BinPtrs bin;
-  ImgPtrs img;
-  bin_layout((size_t)num_rendered, gx * gy, &bin, (char*)binning_buffer);
-  img_layout(W, H, &img, (char*)image_buffer);
+  const Layouts L(0, num_rendered, size_camera(W, H), nullptr, binning_buffer, image_buffer);  // no geometry
   if (slots && num_rendered > 0)
-    check_hip(hipMemcpyAsync(slots, bin.point_list, sizeof(uint32_t) * (size_t)num_rendered, hipMemcpyDeviceToDevice,
+    check_hip(hipMemcpyAsync(slots, L.bin.point_list, sizeof(uint32_t) * (size_t)num_rendered, hipMemcpyDeviceToDevice,
                              st), "copy");
   if (tile_cut)
-    check_hip(hipMemcpyAsync(tile_cut, img.tile_cut, sizeof(uint32_t) * (size_t)gx * gy, hipMemcpyDeviceToDevice, st),
-              "copy");
+    check_hip(hipMemcpyAsync(tile_cut, L.img.tile_cut, sizeof(uint32_t) * (size_t)gx * gy, hipMemcpyDeviceToDevice,
+                             st), "copy");
   return t_failed ? 1 : 0;
 }
 

@@ -116,8 +116,30 @@ class _Inputs:
             if need_opacity and (self.opacity is None or self.opacity.numel() != self.P):
                 raise RuntimeError("opacities must have shape (P, 1)")
 
-    def common(self):
-        return (_ptr(self.means3D), _ptr(self.sh), _ptr(self.colors), _ptr(self.opacity), _ptr(self.scales))
+    def scene(self, scale_modifier, *colour):
+        """The per-Gaussian argument group of the C entries.  colour: what the entry takes between shs
+        and opacities -- colors_precomp, features_rest (the _split entries), or both in that order."""
+        return (_ptr(self.means3D), _ptr(self.sh), *map(_ptr, colour), _ptr(self.opacity), _ptr(self.scales),
+                float(scale_modifier), _ptr(self.rotations), _ptr(self.cov3D))
+
+    def camera(self, tan_fovx, tan_fovy):
+        return (_ptr(self.view), _ptr(self.proj), _ptr(self.campos), float(tan_fovx), float(tan_fovy))
+
+    def preprocess(self, W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug, st):
+        """The two-call forward's first half (gs_forward_preprocess; _split for split SH rows):
+        (num_rendered, radii, geomBuffer), every radius written by the kernels."""
+        radii = torch.empty((self.P,), dtype=torch.int32, device=self.device)
+        geom = torch.empty((_lib.gs_geom_buffer_bytes(self.P),), dtype=torch.uint8, device=self.device)
+        nr = ctypes.c_longlong(0)
+        split = self.sh_rest is not None
+        _native.check(
+            (_lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)(
+                self.P, int(degree), self.M, _ptr(self.bg), W, H,
+                *self.scene(scale_modifier, self.sh_rest if split else self.colors), *self.camera(tan_fovx, tan_fovy),
+                int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st),
+            "rasterize_gaussians (preprocess)")
+        _LAST_NUM_RENDERED[0] = int(nr.value)
+        return int(nr.value), radii, geom
 
 
 def preprocess_views(backgrounds, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -165,8 +187,7 @@ def preprocess_views(backgrounds, means3D, colors, opacity, scales, rotations, s
         _native.check(
             (_lib.gs_forward_preprocess_views if capacities is None else _lib.gs_forward_preprocess_views_bounded)(
                 K, x.P, int(degree), x.M, arr([y.bg for y in xs]), (ctypes.c_int * K)(*[int(w) for w in image_widths]),
-                (ctypes.c_int * K)(*[int(h) for h in image_heights]), _ptr(x.means3D), _ptr(x.sh), _ptr(x.colors),
-                _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D),
+                (ctypes.c_int * K)(*[int(h) for h in image_heights]), *x.scene(scale_modifier, x.colors),
                 arr([y.view for y in xs]), arr([y.proj for y in xs]), arr([y.campos for y in xs]),
                 (ctypes.c_float * K)(*[float(t) for t in tan_fovx]), (ctypes.c_float * K)(*[float(t) for t in tan_fovy]),
                 int(bool(prefiltered)), arr(radii), arr(geoms), nr, int(bool(debug)), _stream(dev), vst),
@@ -307,15 +328,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         geom = torch.empty((_lib.gs_geom_buffer_bytes(x.P),), **u8)
         binning = torch.empty((_lib.gs_binning_buffer_bytes(capacity, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
-        split = x.sh_rest is not None
         with torch.cuda.device(dev):
             _native.check(
                 _lib.gs_forward_bounded(
-                    x.P, int(degree), x.M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh), _ptr(x.sh_rest),
-                    _ptr(x.colors), _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations),
-                    _ptr(x.cov3D), _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
-                    int(bool(prefiltered)), _ptr(radii), _ptr(geom), capacity, _ptr(binning), _ptr(img),
-                    _ptr(out_color), int(bool(debug)), _stream(dev)),
+                    x.P, int(degree), x.M, _ptr(x.bg), W, H, *x.scene(scale_modifier, x.sh_rest, x.colors),
+                    *x.camera(tan_fovx, tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom), capacity,
+                    _ptr(binning), _ptr(img), _ptr(out_color), int(bool(debug)), _stream(dev)),
                 "rasterize_gaussians (bounded)")
         return capacity, out_color, radii, geom, binning, img
     with torch.cuda.device(dev):
@@ -332,33 +350,19 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                     raise RuntimeError("rasterize_gaussians: the prepared view was binned for another image size")
                 _native.check(
                     _lib.gs_forward_render_binned(
-                        x.P, _ptr(x.bg), W, H, _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx),
-                        float(tan_fovy), _ptr(geom), num_rendered, _ptr(binning), _ptr(img), _ptr(out_color),
-                        int(bool(bounded)), int(bool(debug)), st),
+                        x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(geom), num_rendered, _ptr(binning),
+                        _ptr(img), _ptr(out_color), int(bool(bounded)), int(bool(debug)), st),
                     "rasterize_gaussians (render)")
                 return num_rendered, out_color, radii, geom, binning, img
         else:
-            radii = torch.empty((x.P,), dtype=torch.int32, device=dev)
-            geom = torch.empty((_lib.gs_geom_buffer_bytes(x.P),), **u8)
-            nr = ctypes.c_longlong(0)
-            split = x.sh_rest is not None
-            _native.check(
-                (_lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)(
-                    x.P, int(degree), x.M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh),
-                    _ptr(x.sh_rest) if split else _ptr(x.colors),
-                    _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D),
-                    _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
-                    int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st),
-                "rasterize_gaussians (preprocess)")
-            num_rendered = int(nr.value)
-            _LAST_NUM_RENDERED[0] = num_rendered
+            num_rendered, radii, geom = x.preprocess(W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered,
+                                                     debug, st)
         binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
         _native.check(
             (_lib.gs_forward_render_bounded if bounded else _lib.gs_forward_render)(
-                x.P, _ptr(x.bg), W, H, _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
-                _ptr(radii), _ptr(geom), num_rendered, _ptr(binning), _ptr(img), _ptr(out_color),
-                int(bool(debug)), st),
+                x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(radii), _ptr(geom), num_rendered,
+                _ptr(binning), _ptr(img), _ptr(out_color), int(bool(debug)), st),
             "rasterize_gaussians (render)")
     return num_rendered, out_color, radii, geom, binning, img
 
@@ -381,29 +385,16 @@ def rasterize_gaussians_aux(background, means3D, colors, opacity, scales, rotati
     # every pixel of the three images and every radius is written by the kernels
     out_color = torch.empty((3, H, W), **f32)
     invdepth, alpha = torch.empty((1, H, W), **f32), torch.empty((1, H, W), **f32)
-    radii = torch.empty((x.P,), dtype=torch.int32, device=dev)
-    geom = torch.empty((_lib.gs_geom_buffer_bytes(x.P),), **u8)
-    nr = ctypes.c_longlong(0)
-    split = x.sh_rest is not None
     with torch.cuda.device(dev):
         st = _stream(dev)
-        _native.check(
-            (_lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)(
-                x.P, int(degree), x.M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh),
-                _ptr(x.sh_rest) if split else _ptr(x.colors),
-                _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D),
-                _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
-                int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st),
-            "rasterize_gaussians (preprocess)")
-        num_rendered = int(nr.value)
-        _LAST_NUM_RENDERED[0] = num_rendered
+        num_rendered, radii, geom = x.preprocess(W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug,
+                                                 st)
         binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
         _native.check(
             _lib.gs_forward_render_aux(
-                x.P, _ptr(x.bg), W, H, _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
-                _ptr(radii), _ptr(geom), num_rendered, _ptr(binning), _ptr(img), _ptr(out_color), _ptr(invdepth),
-                _ptr(alpha), int(bool(debug)), st),
+                x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(radii), _ptr(geom), num_rendered,
+                _ptr(binning), _ptr(img), _ptr(out_color), _ptr(invdepth), _ptr(alpha), int(bool(debug)), st),
             "rasterize_gaussians (render, aux outputs)")
     return num_rendered, out_color, radii, geom, binning, img, invdepth, alpha
 
@@ -491,45 +482,33 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     R = binning_layout_count(R, binningBuffer, W, H)
     with torch.cuda.device(dev):
         st = _stream(dev)
-        grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes(R),), dtype=torch.uint8, device=dev)
         wait = ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None
+        # the argument groups every variant shares; the calls differ in the colour sources, the aux
+        # gradients in front of the scratch and (split SH rows: SH colours) the dL/dcolors output
+        head = (P, int(degree), M, _ptr(x.bg), W, H)
+        bufs = x.camera(tan_fovx, tan_fovy) + (_ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer),
+                                               _ptr(imageBuffer), _ptr(dpix))
+        grads = [_ptr(o[n]) for n in GRAD_NAMES]
+        tail = (acc, wait, int(bool(debug)), st)
+        what = "rasterize_gaussians_backward"
         if aux_grads is not None:
             d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
             for t in (d_inv, d_alpha):
                 if t is not None and t.numel() != H * W:
                     raise RuntimeError("aux gradients must have shape (1, H, W)")
             grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes_aux(R, P),), dtype=torch.uint8, device=dev)
-            _native.check(
-                _lib.gs_backward_accumulate_aux(
-                    P, int(degree), M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh), _ptr(x.sh_rest),
-                    _ptr(x.colors), _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations),
-                    _ptr(x.cov3D), _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy),
-                    _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix),
-                    _ptr(d_inv), _ptr(d_alpha), _ptr(grad_scratch), _ptr(o["means2D"]), _ptr(o["colors"]),
-                    _ptr(o["opacity"]), _ptr(o["means3D"]), _ptr(o["cov3D"]), _ptr(o["sh"]), _ptr(o["scales"]),
-                    _ptr(o["rotations"]), acc, wait, int(bool(debug)), st),
-                "rasterize_gaussians_backward (aux outputs)")
-            return ret
-        if x.sh_rest is not None:  # split SH rows: SH colours, so no dL/dcolors output
-            _native.check(
-                _lib.gs_backward_accumulate_split(
-                    P, int(degree), M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh), _ptr(x.sh_rest),
-                    _ptr(x.opacity), _ptr(x.scales), float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D),
-                    _ptr(x.view), _ptr(x.proj), _ptr(x.campos), float(tan_fovx), float(tan_fovy), _ptr(radii),
-                    _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix), _ptr(grad_scratch),
-                    _ptr(o["means2D"]), _ptr(o["opacity"]), _ptr(o["means3D"]), _ptr(o["cov3D"]), _ptr(o["sh"]),
-                    _ptr(o["scales"]), _ptr(o["rotations"]), acc, wait, int(bool(debug)), st),
-                "rasterize_gaussians_backward")
-            return ret
-        _native.check(
-            _lib.gs_backward_accumulate(
-                P, int(degree), M, _ptr(x.bg), W, H, _ptr(x.means3D), _ptr(x.sh), _ptr(x.colors), _ptr(x.opacity),
-                _ptr(x.scales), float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D), _ptr(x.view), _ptr(x.proj),
-                _ptr(x.campos), float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), int(R),
-                _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix), _ptr(grad_scratch), _ptr(o["means2D"]),
-                _ptr(o["colors"]), _ptr(o["opacity"]), _ptr(o["means3D"]), _ptr(o["cov3D"]), _ptr(o["sh"]),
-                _ptr(o["scales"]), _ptr(o["rotations"]), acc, wait, int(bool(debug)), st),
-            "rasterize_gaussians_backward")
+            rc = _lib.gs_backward_accumulate_aux(*head, *x.scene(scale_modifier, x.sh_rest, x.colors), *bufs,
+                                                 _ptr(d_inv), _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail)
+            what += " (aux outputs)"
+        else:
+            grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes(R),), dtype=torch.uint8, device=dev)
+            if x.sh_rest is not None:
+                rc = _lib.gs_backward_accumulate_split(*head, *x.scene(scale_modifier, x.sh_rest), *bufs,
+                                                       _ptr(grad_scratch), grads[0], *grads[2:], *tail)
+            else:
+                rc = _lib.gs_backward_accumulate(*head, *x.scene(scale_modifier, x.colors), *bufs, _ptr(grad_scratch),
+                                                 *grads, *tail)
+        _native.check(rc, what)
     return ret
 
 
