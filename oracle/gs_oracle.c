@@ -32,6 +32,7 @@
  *   - Gradient sums over pixels / tiles are accumulated in double here (order-independent
  *     reference); the GPU sums in fp32 in its own order -> tolerance documented in tests.
  */
+#include <float.h>
 #include <math.h>
 #include <omp.h>
 #include <stdint.h>
@@ -907,10 +908,12 @@ void oracle_mark_visible(int P, const float* means, const float* view, const flo
 }
 
 /* simple-knn distCUDA2 restatement: mean of the squared distances to the 3 nearest other points
- * (brute force O(P^2); test sizes only).  Ref call site: scene/gaussian_model.py:134-135. */
+ * (brute force O(P^2); test sizes only).  Ref call site: scene/gaussian_model.py:134-135.
+ * A missing neighbour (P < 4) counts as FLT_MAX, upstream's initial value, not as infinity: P = 3
+ * gives (d0 + d1 + FLT_MAX) / 3 = FLT_MAX / 3 (finite), P <= 2 overflows to +inf. */
 void oracle_knn_mean_dist2(int P, const float* pts, float* out) {
     for (int i = 0; i < P; i++) {
-        float best[3] = {INFINITY, INFINITY, INFINITY};
+        float best[3] = {FLT_MAX, FLT_MAX, FLT_MAX};
         for (int j = 0; j < P; j++) {
             if (j == i) continue;
             float dx = pts[3 * j] - pts[3 * i], dy = pts[3 * j + 1] - pts[3 * i + 1], dz = pts[3 * j + 2] - pts[3 * i + 2];
