@@ -1606,21 +1606,26 @@ int gs_densify_emit(int P, int N, const uint32_t* totals_host, const uint8_t* fl
   if (widths_host[DT_XYZ] != 3 || widths_host[DT_FDC] != 3 || widths_host[DT_OPACITY] != 1 ||
       widths_host[DT_SCALING] != 3 || widths_host[DT_ROT] != 4 || widths_host[DT_FREST] < 0)
     return set_error("densify: row widths must be xyz 3, f_dc 3, f_rest 3K, opacity 1, scaling 3, rotation 4"), 1;
+  // P' == 0 (everything pruned): the outputs are zero-row tensors, whose data pointers may be NULL
+  const bool rows = (uint64_t)totals_host[0] + totals_host[1] + (uint64_t)N * totals_host[3] != 0;
   DensTensors t;
   for (int q = 0; q < DENS_TENSORS; q++) {
     t.src[q] = params_host[q];
     t.dst[q] = out_params_host[q];
     t.width[q] = widths_host[q];
     const bool has_m = exp_avg_host && exp_avg_host[q];
-    if (has_m && (!exp_avg_sq_host || !exp_avg_sq_host[q] || !out_exp_avg_host || !out_exp_avg_host[q] ||
-                  !out_exp_avg_sq_host || !out_exp_avg_sq_host[q]))
+    if (has_m && (!exp_avg_sq_host || !exp_avg_sq_host[q] ||
+                  (rows && (!out_exp_avg_host || !out_exp_avg_host[q] || !out_exp_avg_sq_host ||
+                            !out_exp_avg_sq_host[q]))))
       return set_error("densify: incomplete optimizer state pointers"), 1;
     t.m_src[q] = has_m ? exp_avg_host[q] : nullptr;
     t.v_src[q] = has_m ? exp_avg_sq_host[q] : nullptr;
-    t.m_dst[q] = has_m ? out_exp_avg_host[q] : nullptr;
-    t.v_dst[q] = has_m ? out_exp_avg_sq_host[q] : nullptr;
-    if ((!t.src[q] || !t.dst[q]) && t.width[q] > 0) return set_error("densify: missing parameter pointer"), 1;
+    t.m_dst[q] = has_m && rows ? out_exp_avg_host[q] : nullptr;
+    t.v_dst[q] = has_m && rows ? out_exp_avg_sq_host[q] : nullptr;
+    if ((!t.src[q] || (rows && !t.dst[q])) && t.width[q] > 0)
+      return set_error("densify: missing parameter pointer"), 1;
   }
+  if (!rows) return 0;  // nothing to write: no launch
   DensCounts n{totals_host[0], totals_host[1], totals_host[2], totals_host[3]};
   const DensifyParams dp = make_dens_params(0, 0, 0, 0, 0, 0, N);
   densify_emit(P, N, dp, n, flags, block_counts, samples, t, (hipStream_t)stream);

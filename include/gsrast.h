@@ -578,7 +578,12 @@ int gs_activate_backward(int P, int sh_rest, const float* dL_dshs, const float* 
  *     samples = torch.normal(mean=zeros, std=stds) exactly as gaussian_model.py:358-360 does.
  *  3. gs_densify_emit: writes the final rows (P' = totals[0] + totals[1] + N * totals[3]) of the six
  *     parameter tensors in order xyz, f_dc, f_rest, opacity, scaling, rotation (row widths
- *     3, 3, 3K, 1, 3, 4) and of their Adam moments (NULL entries: group without state). */
+ *     3, 3, 3K, 1, 3, 4) and of their Adam moments (NULL entries: group without state).
+ *     When P' == 0 (everything pruned) the entries of out_params_host / out_exp_avg_host /
+ *     out_exp_avg_sq_host may be NULL (zero-row tensors have no storage): the call checks its other
+ *     arguments as usual, launches nothing and returns 0.  With P' > 0 a NULL output of positive
+ *     width is refused ("missing parameter pointer").  A relaxation within ABI v17: no entry point
+ *     or argument changed. */
 size_t gs_densify_block_count(int P);
 int gs_densify_classify(int P, const float* grad_accum, const float* denom, const float* opacity_raw,
                         const float* scaling_raw, double grad_threshold, double pd_extent, double min_opacity,

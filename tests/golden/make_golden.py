@@ -17,6 +17,11 @@ Reference functions exercised (all on CPU):
                                        on CPU: the module is loaded with empty stand-ins for the two
                                        imports it does not use on this path (plyfile, simple_knn._C) and
                                        the same device="cuda"-dropping torch proxy
+                                       (densify_golden.npz); the same call on the constructed edge rows
+                                       of tests/constructed_densify.py and on a model whose rows all
+                                       fall under min_opacity -- the reference does not raise there, it
+                                       returns zero-row tensors (densify_edges_golden.npz; made alone by
+                                       `make_golden.py densify_edges`, the other files are not rewritten)
   - gaussian_renderer/__init__.py:18-100  render() with the reference's own Camera (scene/cameras.py:
                                        17-57; its .cuda() calls made no-ops) and GaussianModel getters
                                        (:95-118); a recording stand-in for diff_gaussian_rasterization
@@ -246,6 +251,70 @@ def densify_vectors(gm_mod):
     np.savez_compressed(os.path.join(OUT, "densify_golden.npz"), **out)
 
 
+def _densify_case(gm_mod, out, case, arrays, grads, args, seed):
+    """One reference densify_and_prune on CPU: Adam state from two steps (as densify_vectors), then
+    the parameters set to `arrays` (the steps would move the constructed ties), the call, the outputs."""
+    attrs = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
+    thr, min_op, extent, screen = args
+    m = gm_mod.GaussianModel(3)
+    for n, attr in zip(DENSIFY_NAMES, attrs):
+        setattr(m, attr, torch.nn.Parameter(torch.tensor(arrays[n]).requires_grad_(True)))
+    m.percent_dense = 0.01
+    groups = [{"params": [getattr(m, a)], "lr": lr, "name": n} for n, a, lr in zip(DENSIFY_NAMES, attrs, DENSIFY_LRS)]
+    m.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+    for _ in range(2):
+        for grp in m.optimizer.param_groups:
+            grp["params"][0].grad = grads[grp["name"]].clone()
+        m.optimizer.step()
+    for grp in m.optimizer.param_groups:
+        n, p = grp["name"], grp["params"][0]
+        with torch.no_grad():
+            p.copy_(torch.tensor(arrays[n]))
+        p.grad = None
+        out[f"{case}_in_{n}"] = p.detach().numpy().copy()
+        st = m.optimizer.state[p]
+        out[f"{case}_in_{n}_exp_avg"] = st["exp_avg"].numpy().copy()
+        out[f"{case}_in_{n}_exp_avg_sq"] = st["exp_avg_sq"].numpy().copy()
+    m.xyz_gradient_accum = torch.tensor(arrays["accum"])
+    m.denom = torch.tensor(arrays["denom"])
+    m.max_radii2D = torch.tensor(arrays["max_radii2D"])
+    out[f"{case}_in_accum"], out[f"{case}_in_denom"], out[f"{case}_in_max_radii2D"] = (
+        arrays["accum"], arrays["denom"], arrays["max_radii2D"])
+    out[f"{case}_args"] = np.array([thr, min_op, extent, -1.0 if screen is None else screen, seed], np.float64)
+    torch.manual_seed(seed)
+    m.densify_and_prune(thr, min_op, extent, screen)
+    for grp in m.optimizer.param_groups:
+        n = grp["name"]
+        out[f"{case}_out_{n}"] = grp["params"][0].detach().numpy()
+        st = m.optimizer.state[grp["params"][0]]
+        out[f"{case}_out_{n}_exp_avg"] = st["exp_avg"].numpy()
+        out[f"{case}_out_{n}_exp_avg_sq"] = st["exp_avg_sq"].numpy()
+        out[f"{case}_out_{n}_step"] = np.array(float(st["step"]))
+    out[f"{case}_out_sizes"] = np.array([m.xyz_gradient_accum.shape[0], m.denom.shape[0], m.max_radii2D.shape[0]])
+
+
+def densify_edges_vectors(gm_mod):
+    """The reference's verdict on the constructed edge rows (tests/constructed_densify.py: every row
+    kind and every tie, 325 rows) and on a model that ends empty (all rows under min_opacity).
+    Writes densify_edges_golden.npz only; run alone with
+        python tests/golden/make_golden.py densify_edges
+    The reference takes N = 2 and, in the args row, a screen size of -1 stands for None as in
+    densify_golden.npz."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import constructed_densify as CD
+
+    out = {}
+    for case, c, seed in (("edges", CD.edges_scene(2, 20.0), 21), ("edges_noscreen", CD.edges_scene(2, None, P=130), 22),
+                          ("empty", CD.make_case("empty", CD.mix(40, 10, CD.ALL_TRANSPARENT), 2, 20.0), 23)):
+        arrays = c.arrays(15)
+        g = torch.Generator().manual_seed(seed)
+        grads = {n: torch.randn(arrays[n].shape, generator=g) for n in DENSIFY_NAMES}
+        _densify_case(gm_mod, out, case, arrays, grads, c.args(), seed)
+        out[f"{case}_kinds"] = c.kinds.astype(np.int16)
+        assert out[f"{case}_out_sizes"][0] == c.P_out, (case, out[f"{case}_out_sizes"], c.P_out)
+    np.savez_compressed(os.path.join(OUT, "densify_edges_golden.npz"), **out)
+
+
 # render() adapter cases: (W, H, fovy_deg, camera position, target or None for R=I/T=0, sh degree
 # active/max, scale_modifier, compute_cov3D_python, convert_SHs_python)
 RENDER_CASES = {
@@ -363,10 +432,15 @@ def render_vectors():
 
 if __name__ == "__main__":
     sh_utils, gu, gfx = _import_ref()
+    if sys.argv[1:] == ["densify_edges"]:  # the one new file; the others keep their host's last bits
+        densify_edges_vectors(_ref_gaussian_model())
+        print("wrote densify_edges_golden.npz")
+        sys.exit(0)
     sh_vectors(sh_utils)
     cov_vectors(gu)
     camera_vectors(gfx)
     loss_vectors()
     densify_vectors(_ref_gaussian_model())
+    densify_edges_vectors(_ref_gaussian_model())
     render_vectors()
     print("wrote", sorted(f for f in os.listdir(OUT) if f.endswith(".npz")))

@@ -12,6 +12,17 @@ Chain of pins:
     (R(q) @ sample + xyz: torch.bmm's reduction order is the library's), which is held to
     rtol 1e-6 / atol 1e-6.  (The child scaling divides by 0.8 N the way torch does on the device:
     a tensor divided by a Python scalar is multiplied by the float reciprocal there.)
+
+Covered here: two golden scenes (300 / 400 rows) and random draws at P = 1, 255, 5000 and 200,003,
+all with one classify block per scan thread; the host-side argument checks of the three C entries
+(an empty result, P' = 0, is accepted with null outputs).  Covered by the constructed cases
+(tests/constructed_densify.py, test_constructed_densify.py, test_gpu_constructed_densify.py): every
+comparison on its bound, inf / NaN / negative gradients, the world-size prune of parents and
+children, empty classes and an empty result, whole waves and blocks of one class, N = 1..3, f_rest
+of width 0, partial Adam state, and the scan's sequential part (P > 262,144, up to 5,000,000).
+The reference's verdict on those edge rows is tests/golden/densify_edges_golden.npz
+(test_oracle_matches_reference_golden_edges).  Not covered anywhere: an exact tie of the child-prune
+bound (exp(log(s * inv)) is no round trip); the multi-rank sample broadcast is in test_gpu_multiview.py.
 """
 import numpy as np
 import pytest
@@ -57,12 +68,16 @@ def _model_from(arrays: dict, device, with_state=True, step=2.0):
     return m
 
 
-def _golden_inputs(case):
+def _edges_golden():
+    return np.load(__file__.rsplit("/", 1)[0] + "/golden/densify_edges_golden.npz", allow_pickle=False)
+
+
+def _golden_inputs(case, G=G):
     pre = f"{case}_in_"
     return {k[len(pre):]: G[k] for k in G.files if k.startswith(pre)}
 
 
-def _args(case):
+def _args(case, G=G):
     thr, min_op, extent, screen, seed = G[f"{case}_args"]
     return float(thr), float(min_op), float(extent), (None if screen < 0 else float(screen)), int(seed)
 
@@ -77,10 +92,9 @@ def _check_model_structure(m):
     assert not m.xyz_gradient_accum.any() and not m.denom.any() and not m.max_radii2D.any()
 
 
-@pytest.mark.parametrize("case", ["a", "b"])
-def test_oracle_matches_reference_golden(case):
-    thr, min_op, extent, screen, seed = _args(case)
-    m = _model_from(_golden_inputs(case), "cpu")
+def _oracle_matches_golden(G, case):
+    thr, min_op, extent, screen, seed = _args(case, G)
+    m = _model_from(_golden_inputs(case, G), "cpu")
     torch.manual_seed(seed)
     DO.densify_and_prune(m, thr, min_op, extent, screen)
     _check_model_structure(m)
@@ -97,15 +111,84 @@ def test_oracle_matches_reference_golden(case):
         np.testing.assert_array_equal(st["exp_avg"].numpy(), G[f"{case}_out_{n}_exp_avg"], err_msg=n)
         np.testing.assert_array_equal(st["exp_avg_sq"].numpy(), G[f"{case}_out_{n}_exp_avg_sq"], err_msg=n)
         assert float(st["step"]) == float(G[f"{case}_out_{n}_step"])
+    return m
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_oracle_matches_reference_golden(case):
+    _oracle_matches_golden(G, case)
+
+
+@pytest.mark.parametrize("case", ["edges", "edges_noscreen", "empty"])
+def test_oracle_matches_reference_golden_edges(case):
+    """The reference's own verdict on every constructed row kind and tie (densify_edges_golden.npz),
+    same bounds as above.  The fixture's inputs are the builder's, and its row count the builder's P'."""
+    import constructed_densify as CD
+
+    E = _edges_golden()
+    m = _oracle_matches_golden(E, case)
+    kinds = E[f"{case}_kinds"].astype(np.int64)
+    _, _, _, screen, _ = _args(case, E)
+    c = CD.make_case(case, kinds, 2, screen)
+    if case.startswith("edges"):
+        assert set(kinds) == set(range(len(CD.KIND_NAMES))) and len(kinds) <= 330
+        assert np.array_equal(kinds, CD.edges_scene(2, screen, P=len(kinds)).kinds)
+    else:
+        assert c.P_out == 0 and m._features_rest.shape == (0, 15, 3)
+    want = c.arrays(15)
+    for k in ("accum", "denom", "max_radii2D") + DO.NAMES:
+        np.testing.assert_array_equal(E[f"{case}_in_{k}"], want[k], err_msg=k)
+    assert int(E[f"{case}_out_sizes"][0]) == c.P_out
+    # the reference's copied rows are the builder's gather (the moments are those of the fixture)
+    n_copy = int(c.totals[0] + c.totals[1])
+    for n in DO.NAMES:
+        got, gathered = E[f"{case}_out_{n}"], want[n][c.src_rows]
+        if n in HOST_ROUNDED:
+            got, gathered = got[:n_copy], gathered[:n_copy]
+        np.testing.assert_array_equal(got, gathered, err_msg=n)
+        mom = E[f"{case}_out_{n}_exp_avg"]
+        np.testing.assert_array_equal(mom[:c.n_orig], E[f"{case}_in_{n}_exp_avg"][c.src_rows[:c.n_orig]])
+        assert not mom[c.n_orig:].any()
 
 
 def test_densify_abi_validation_without_gpu():
+    import ctypes
+
     from diff_gaussian_rasterization import _native
 
     lib = _native.load()
     assert lib.gs_densify_block_count(0) == 0 and lib.gs_densify_block_count(257) == 2
     rc = lib.gs_densify_classify(10, None, None, None, None, 2e-4, 0.02, 0.005, 0.2, 0, 0.0, 2, None, None, None, None)
     assert rc != 0 and "missing" in _native.last_error()
+
+    # gs_densify_emit: the argument checks come before any launch, so host memory stands in here
+    buf = (ctypes.c_float * 64)()
+    some = ctypes.cast(buf, ctypes.c_void_p)
+    six = lambda v: ctypes.cast((ctypes.c_void_p * 6)(*[v] * 6), ctypes.c_void_p)  # noqa: E731
+    widths = ctypes.cast((ctypes.c_int * 6)(3, 3, 45, 1, 3, 4), ctypes.c_void_p)
+    tot = lambda *t: ctypes.cast((ctypes.c_uint32 * 4)(*t), ctypes.c_void_p)  # noqa: E731
+
+    def emit(totals, outs, m_in=None, m_out=None, w=widths, samples=None, src=some):
+        return lib.gs_densify_emit(10, 2, totals, some, some, samples, six(src), six(m_in), six(m_in), six(outs),
+                                   six(m_out), six(m_out), w, None)
+
+    # an empty result (zero-row outputs have null data pointers): accepted, nothing launched
+    assert emit(tot(0, 0, 0, 0), None) == 0, _native.last_error()
+    assert emit(tot(0, 0, 4, 0), None, samples=some) == 0, _native.last_error()  # splits, no kept child
+    assert emit(tot(0, 0, 0, 0), None, m_in=some, m_out=None) == 0, _native.last_error()  # with Adam state
+    # ... its other checks unchanged
+    assert emit(tot(0, 0, 4, 0), None) != 0 and "split samples missing" in _native.last_error()
+    assert emit(tot(0, 0, 0, 0), None, src=None) != 0 and "missing parameter pointer" in _native.last_error()
+    bad = ctypes.cast((ctypes.c_int * 6)(3, 3, 45, 1, 3, 3), ctypes.c_void_p)
+    assert emit(tot(0, 0, 0, 0), None, w=bad) != 0 and "row widths" in _native.last_error()
+    assert lib.gs_densify_emit(10, 2, None, some, some, None, six(some), None, None, six(None), None, None, widths,
+                               None) != 0 and "missing argument" in _native.last_error()
+    # a null output with rows to write is still refused, with the same text
+    for t in ((1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 1)):
+        assert emit(tot(*t), None, samples=some) != 0
+        assert "densify: missing parameter pointer" in _native.last_error(), _native.last_error()
+    assert emit(tot(1, 0, 0, 0), some, m_in=some, m_out=None) != 0
+    assert "incomplete optimizer state pointers" in _native.last_error()
 
 
 def _compare_models(ours, ref, xyz_tol=True):
@@ -126,11 +209,15 @@ def _compare_models(ours, ref, xyz_tol=True):
             assert float(s1["step"]) == float(s2["step"])
 
 
-def _run_both(arrays, device, thr, min_op, extent, screen, seed, N=2, with_state=True):
+def _run_both(arrays, device, thr, min_op, extent, screen, seed, N=2, with_state=True, prepare=None):
+    """prepare(model): applied to both models before the calls (e.g. drops some groups' Adam state)"""
     from gs_train import densify_and_prune
 
     ours = _model_from(arrays, device, with_state)
     ref = _model_from(arrays, device, with_state)
+    if prepare is not None:
+        prepare(ours)
+        prepare(ref)
     torch.cuda.manual_seed(seed)
     DO.densify_and_prune(ref, thr, min_op, extent, screen, N)
     torch.cuda.manual_seed(seed)
