@@ -1158,6 +1158,46 @@ int gs_backward_accumulate_split(int P, int D, int M, const float* background, i
       wait_event, debug, (hipStream_t)stream);
 }
 
+size_t gs_camera_grad_scratch_bytes(int P) { return camera_grad_scratch_bytes((size_t)(P > 0 ? P : 0)); }
+
+int gs_backward_camera(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                       const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
+                       int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                       int debug, void* stream) {
+  const GaussianArgs g = make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales,
+                                    scale_modifier, rotations, cov3D_precomp);
+  const CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
+  hipStream_t st = (hipStream_t)stream;
+  clear_error(debug);
+  if (!validate(g, c, false)) return 1;
+  if (!dL_dviewmatrix || !dL_dprojmatrix) return set_error("missing gradient output pointer"), 1;
+  if (P == 0) {  // no Gaussians: zero gradients
+    if (!check_hip(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), st), "hipMemsetAsync") ||
+        !check_hip(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), st), "hipMemsetAsync") ||
+        (dL_dcampos && !check_hip(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), st), "hipMemsetAsync")))
+      return 1;
+    return 0;
+  }
+  if (!geom_buffer || !scratch || (aux_valid && !aux_grad_buffer)) return set_error("missing buffer pointer"), 1;
+  if (((uintptr_t)scratch) & 15) return set_error("camera grad: scratch must be 16-byte aligned"), 1;
+  if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
+  GeomPtrs geo;
+  geom_layout((size_t)P, &geo, (char*)geom_buffer);
+  const float* gsum_aux = nullptr;
+  if (aux_valid) {
+    size_t o_sum = 0;
+    grad_layout_aux((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)P, nullptr, &o_sum);
+    gsum_aux = (const float*)((const char*)aux_grad_buffer + o_sum);
+  }
+  // (without instances the aux backward sums nothing: no depth term, as in backward_impl)
+  bwd_camera(g, c, geo, num_rendered > 0 ? gsum_aux : nullptr, (double*)scratch, dL_dviewmatrix, dL_dprojmatrix,
+             dL_dcampos, st);
+  return t_failed ? 1 : 0;
+}
+
 int gs_backward_render(int P, int D, int M, const float* background, int W, int H, const float* viewmatrix,
                        const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
                        const void* geom_buffer, long long num_rendered, const void* binning_buffer,

@@ -731,9 +731,18 @@ __device__ __forceinline__ void cov3d_backward(float sx, float sy, float sz, flo
 // Camera-dependent part of the per-Gaussian backward (upstream computeCov2DCUDA + the projection
 // term of preprocessCUDA's backward, order identical to oracle/gs_oracle.c): conic gradient ->
 // cov2D -> cov3D gradient (dcv) and the view-space mean gradient incl. the NDC-mean term (dmean).
+// CAM (k_camera_grad): the same values are also handed out in `ct`, the factors of the camera
+// gradient's per-Gaussian terms; the plain instantiation is the code it was before.
+struct CamTerms {
+  float dt[3];            // dL/dt, t = (m, 1) view: (dL_dtx, dL_dty, dL_dtz), clamp masks included
+  float dT0[3], dT1[3];   // dL/dT rows, T = J W
+  float J00, J02, J11, J12;  // the Jacobian's entries as cov2d forms them (clamped tx, ty)
+  float m_w, mul1, mul2;  // the projection's 1 / w and its two quotient factors
+};
+template <bool CAM = false>
 __device__ __forceinline__ void camera_grads(const CameraArgs& c, float px, float py, float pz, const float* cov3,
                                              float dcon0, float dcon1, float dcon2, float dm2x, float dm2y,
-                                             float* dcv, float* dmean) {
+                                             float* dcv, float* dmean, CamTerms* ct = nullptr) {
 #pragma unroll
   for (int k = 0; k < 6; k++) dcv[k] = 0.f;
   // conic -> cov2D -> cov3D and view-space mean
@@ -791,6 +800,15 @@ __device__ __forceinline__ void camera_grads(const CameraArgs& c, float px, floa
   dmean[0] = dmean[0] + pm0;
   dmean[1] = dmean[1] + pm1;
   dmean[2] = dmean[2] + pm2;
+  if constexpr (CAM) {
+    ct->dt[0] = dL_dtx, ct->dt[1] = dL_dty, ct->dt[2] = dL_dtz;
+#pragma unroll
+    for (int r = 0; r < 3; r++) ct->dT0[r] = dT0[r], ct->dT1[r] = dT1[r];
+    const float z2 = cv.tz * cv.tz;
+    ct->J00 = c.fx / cv.tz, ct->J02 = -(c.fx * cv.tx) / z2;
+    ct->J11 = c.fy / cv.tz, ct->J12 = -(c.fy * cv.ty) / z2;
+    ct->m_w = m_w, ct->mul1 = mul1, ct->mul2 = mul2;
+  }
 }
 
 // one gradient output element: written, or (GS_ACC bit set for the output) added to the caller's
@@ -1564,6 +1582,205 @@ void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& 
       GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_reg<3>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, out);
       break;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// camera gradient (gs_backward_camera): dL/dviewmatrix, dL/dprojmatrix, dL/dcampos of one view
+// ------------------------------------------------------------------------------------------
+
+// One lane per Gaussian in index order, after the view's record sums exist.  The lane forms its
+// fp32 terms from the values camera_grads / sh_backward hand to the plain backward:
+//   view[r][k]  (12: r = 0..3, k = 0..2)  ph_r dL/dt_k + (r < 3) (J[0][k] dT0[r] + J[1][k] dT1[r])
+//                                         (+ ph_r dz for k = 2 with an aux inverse-depth sum, the
+//                                         dz of k_depth_chain_aux),   ph = (m, 1)
+//   proj[r][c]  (12: c = 0, 1, 3)         ph_r m_w dm2x, ph_r m_w dm2y, -ph_r (mul1 dm2x + mul2 dm2y)
+//   campos[k]   (3, DEG >= 0 only)        -shm[k]: the SH row is read for these alone
+// (view column 3 and proj column 2 are structural zeros, written by the finish kernel).  A lane
+// without instances, or past P, contributes exact zeros.  The sums are taken in fp64 in a fixed
+// order: the workgroup's terms are transposed through LDS (row stride 264 floats: the 32 lanes of
+// a half wave read 32 different banks), 8 threads per sum add 32 terms each (seg, seg + 8, ...),
+// one thread adds the 8 segments, and the workgroup writes one row of CAMG_ROW doubles.
+// -DGS_CAMGRAD_BUTTERFLY builds the wave xor-butterfly of fp64 values instead (measured slower:
+// profiles/camera_grad_reduce_ab.txt).
+template <int DEG>  // -1: no campos sums (no SH row read)
+__global__ __launch_bounds__(256) void k_camera_grad(GaussianArgs g, CameraArgs c,
+                                                     const uint32_t* __restrict__ tiles,
+                                                     const uint8_t* __restrict__ clamped,
+                                                     const float* __restrict__ gsum,
+                                                     const float* __restrict__ gsum_aux,
+                                                     const float4* __restrict__ splat,
+                                                     double* __restrict__ partial) {
+  constexpr int NV = DEG < 0 ? 24 : CAMG_SUMS;
+  const int t = (int)threadIdx.x;
+  const int i = blockIdx.x * 256 + t;
+  float v[NV];
+#pragma unroll
+  for (int k = 0; k < NV; k++) v[k] = 0.0f;
+  if (i < g.P && tiles[i] != 0) {
+    const float* rec = gsum + (size_t)i * GRAD_REC;
+    float a[GRAD_REC];
+#pragma unroll
+    for (int k = 0; k < GRAD_REC; k++) a[k] = rec[k];
+    const float dm2x = a[3], dm2y = a[4];
+    const float px = g.means3D[3 * i], py = g.means3D[3 * i + 1], pz = g.means3D[3 * i + 2];
+    float cov3[6];
+    if (g.cov3D) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) cov3[k] = g.cov3D[6 * i + k];
+    } else {
+      cov3d(g.scales[3 * i], g.scales[3 * i + 1], g.scales[3 * i + 2], g.scale_modifier, g.rotations[4 * i],
+            g.rotations[4 * i + 1], g.rotations[4 * i + 2], g.rotations[4 * i + 3], cov3);
+    }
+    float dcv[6], dmean[3];
+    CamTerms ct;
+    camera_grads<true>(c, px, py, pz, cov3, a[5], a[6], a[7], dm2x, dm2y, dcv, dmean, &ct);
+    float dz = 0.0f;
+    if (gsum_aux) {
+      const float z = splat[3 * i + 2].y;
+      dz = -gsum_aux[i] / (z * z);
+    }
+    const float ph[4] = {px, py, pz, 1.0f};
+    const float pc0 = ct.m_w * dm2x, pc1 = ct.m_w * dm2y, pc3 = ct.mul1 * dm2x + ct.mul2 * dm2y;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      float vx = ph[r] * ct.dt[0], vy = ph[r] * ct.dt[1], vz = ph[r] * ct.dt[2];
+      if (r < 3) {
+        vx = vx + ct.J00 * ct.dT0[r];
+        vy = vy + ct.J11 * ct.dT1[r];
+        vz = vz + (ct.J02 * ct.dT0[r] + ct.J12 * ct.dT1[r]);
+      }
+      if (gsum_aux) vz = vz + ph[r] * dz;
+      v[3 * r] = vx, v[3 * r + 1] = vy, v[3 * r + 2] = vz;
+      v[12 + 3 * r] = ph[r] * pc0, v[12 + 3 * r + 1] = ph[r] * pc1, v[12 + 3 * r + 2] = -(ph[r] * pc3);
+    }
+    if constexpr (DEG >= 0) {
+      constexpr int KF = 3 * (DEG + 1) * (DEG + 1);
+      const int rowf = 3 * g.M;
+      const float* src = g.shs + (size_t)i * rowf;
+      float row[KF], unused[KF], shm[3];
+      if ((KF & 3) == 0 && (rowf & 3) == 0 && (((uintptr_t)g.shs) & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < KF / 4; q++) {
+          const float4 w = reinterpret_cast<const float4*>(src)[q];
+          row[4 * q] = w.x, row[4 * q + 1] = w.y, row[4 * q + 2] = w.z, row[4 * q + 3] = w.w;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < KF; k++) row[k] = src[k];
+      }
+      const float dcol[3] = {a[0], a[1], a[2]};
+      // (ACC form: the row is left alone and dL/dsh, which nobody reads here, goes to `unused`)
+      sh_backward<DEG, true, true>(row, g.M, px - c.campos[0], py - c.campos[1], pz - c.campos[2], clamped[i], dcol,
+                                   shm, unused, true);
+      v[24] = -shm[0], v[25] = -shm[1], v[26] = -shm[2];
+    }
+  }
+#ifdef GS_CAMGRAD_BUTTERFLY
+  __shared__ double s_w[4][NV];
+  double d[NV];
+#pragma unroll
+  for (int k = 0; k < NV; k++) d[k] = (double)v[k];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+    for (int k = 0; k < NV; k++) d[k] = d[k] + __shfl_xor(d[k], off, 64);
+  if ((t & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < NV; k++) s_w[t >> 6][k] = d[k];
+  __syncthreads();
+  if (t < CAMG_ROW)
+    partial[(size_t)blockIdx.x * CAMG_ROW + t] = t < NV ? ((s_w[0][t] + s_w[1][t]) + s_w[2][t]) + s_w[3][t] : 0.0;
+#else
+  constexpr int STRIDE = 264;
+  __shared__ float s_v[NV][STRIDE];
+  __shared__ double s_p[NV][8];
+#pragma unroll
+  for (int k = 0; k < NV; k++) s_v[k][t] = v[k];
+  __syncthreads();
+  if (t < NV * 8) {
+    const float* col = &s_v[t >> 3][t & 7];
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 32; k++) acc = acc + (double)col[8 * k];
+    s_p[t >> 3][t & 7] = acc;
+  }
+  __syncthreads();
+  if (t < CAMG_ROW) {
+    double acc = 0.0;
+    if (t < NV)
+#pragma unroll
+      for (int s = 0; s < 8; s++) acc = acc + s_p[t][s];
+    partial[(size_t)blockIdx.x * CAMG_ROW + t] = acc;
+  }
+#endif
+}
+
+// One workgroup of 1024: the nb partial rows summed in fp64 in a fixed order (73 row groups of 14
+// column pairs, each thread over its rows rg, rg + 73, ...: whole 16-B loads of consecutive
+// addresses, looping while rows remain; then the 73 groups in order), and the 35 outputs written as
+// floats, structural zeros included.  One compute unit reads all the rows (875 KB at C3's 3,907):
+// 14.7 us there, 15.3 - 15.6 with 18 groups in 256 threads (profiles/camera_grad_reduce_ab.txt).
+// Under the view's ERR_INVALID flags (no valid instance list: the record sums' rule) the outputs
+// are zeros.
+__global__ __launch_bounds__(1024) void k_camera_grad_finish(const uint32_t* __restrict__ counters,
+                                                            const double* __restrict__ partial, int nb,
+                                                            float* __restrict__ dview, float* __restrict__ dproj,
+                                                            float* __restrict__ dcampos) {
+  constexpr int GROUPS = CAMG_FINISH_THREADS / (CAMG_ROW / 2), PAIRS = CAMG_ROW / 2;
+  __shared__ double s_acc[GROUPS][CAMG_ROW];
+  __shared__ double s_fin[CAMG_ROW];
+  const int t = (int)threadIdx.x;
+  const bool invalid = (counters[CNT_ERR] & ERR_INVALID) != 0;
+  if (t < GROUPS * PAIRS) {
+    const int cp = t % PAIRS, rg = t / PAIRS;
+    double a0 = 0.0, a1 = 0.0;
+    if (!invalid) {
+#pragma unroll 8
+      for (int r = rg; r < nb; r += GROUPS) {
+        const double2 p = reinterpret_cast<const double2*>(partial)[(size_t)r * PAIRS + cp];
+        a0 = a0 + p.x;
+        a1 = a1 + p.y;
+      }
+    }
+    s_acc[rg][2 * cp] = a0;
+    s_acc[rg][2 * cp + 1] = a1;
+  }
+  __syncthreads();
+  if (t < CAMG_ROW) {
+    double a = 0.0;
+    for (int rg = 0; rg < GROUPS; rg++) a = a + s_acc[rg][t];
+    s_fin[t] = a;
+  }
+  __syncthreads();
+  if (t < 16) {
+    dview[t] = (t & 3) < 3 ? (float)s_fin[3 * (t >> 2) + (t & 3)] : 0.0f;
+  } else if (t < 32) {
+    const int u = t - 16, col = u & 3;
+    dproj[u] = col == 2 ? 0.0f : (float)s_fin[12 + 3 * (u >> 2) + (col == 3 ? 2 : col)];
+  } else if (t < 35 && dcampos) {
+    dcampos[t - 32] = (float)s_fin[24 + (t - 32)];
+  }
+}
+
+void bwd_camera(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const float* gsum_aux,
+                double* partial, float* dview, float* dproj, float* dcampos, hipStream_t st) {
+  if (g.P <= 0) return;
+  const int nb = (g.P + 255) / 256;
+  const dim3 grid(nb), block(256);
+  const int deg = (dcampos && g.shs && !g.colors) ? g.D : -1;
+#define GS_CAMG(D)                                                                                            \
+  GS_LAUNCH("camera_grad", k_camera_grad<D>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, gsum_aux, \
+            geo.splat, partial)
+  switch (deg) {
+    case 0: GS_CAMG(0); break;
+    case 1: GS_CAMG(1); break;
+    case 2: GS_CAMG(2); break;
+    case 3: GS_CAMG(3); break;
+    default: GS_CAMG(-1); break;
+  }
+#undef GS_CAMG
+  GS_LAUNCH("camera_grad_finish", k_camera_grad_finish, dim3(1), dim3(CAMG_FINISH_THREADS), 0, st, geo.counters, partial, nb, dview,
+            dproj, dcampos);
 }
 
 }  // namespace gs

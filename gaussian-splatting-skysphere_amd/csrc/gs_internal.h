@@ -536,6 +536,16 @@ void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& 
 // chain's add into dL/dmeans3D (from gsum_aux, summed with the other record sums)
 void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BwdAux& aux,
                      float* dmean3D, hipStream_t st);
+// the camera gradient of one view (gs_backward_camera), after its record sums: 27 sums (12 view, 12
+// proj, 3 campos) in fp64, one row of CAMG_ROW doubles (the 27 and a zero: whole 16-B pairs) per
+// workgroup of 256 Gaussians in `partial`, then one finishing workgroup.  gsum_aux: the aux
+// backward's inverse-depth sums, or null.  dcampos may be null (no SH row is read then).
+constexpr int CAMG_SUMS = 27, CAMG_ROW = 28, CAMG_FINISH_THREADS = 1024;
+inline size_t camera_grad_scratch_bytes(size_t P) {
+  return ((P ? P : 1) + 255) / 256 * CAMG_ROW * sizeof(double);
+}
+void bwd_camera(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const float* gsum_aux,
+                double* partial, float* dview, float* dproj, float* dcampos, hipStream_t st);
 void knn_mean_dist2(int P, const float* pts, float* out, char* scratch, hipStream_t st);
 void ssim_forward(int planes, int H, int W, const float* win11, const float* img1, const float* img2, float* dmaps,
                   float* partial, float* plane_sum, hipStream_t st);

@@ -421,7 +421,8 @@ GS_ACC = {n: 1 << k for k, n in enumerate(GRAD_NAMES)}
 
 def backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                   projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                  imageBuffer, debug, want_all=True, sinks=None, wait_event=None, sh_rest=None, aux_grads=None):
+                  imageBuffer, debug, want_all=True, sinks=None, wait_event=None, sh_rest=None, aux_grads=None,
+                  camera=None):
     """Shared backward.  With want_all=False the gradients that no autograd input can receive
     (colours when SHs drive the colour, cov3D when scale/rotation drive it, ...) are None and
     not computed.  sinks: {name: (buffer, accumulate)} -- that gradient is written into (or, with
@@ -431,10 +432,15 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     (a sink shared with views on other streams).  sh_rest: split SH rows as rasterize_gaussians;
     the `sh` gradient is then that of the concatenation, [P, M, 3].
     aux_grads: (dL_dout_invdepth, dL_dout_alpha) of a rasterize_gaussians_aux forward, either may be
-    None (gs_backward_accumulate_aux, over ctypes)."""
+    None (gs_backward_accumulate_aux, over ctypes).
+    camera: None, or whether dL/dcampos is wanted -- the return then ends with one more item, the
+    view's camera gradients (dL_dviewmatrix [4, 4], dL_dprojmatrix [4, 4], dL_dcampos [3] or None) of
+    gs_backward_camera, run right behind the backward on its stream (over ctypes)."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None
-    if _EXT is not None and not want_all and means3D.is_cuda and aux_grads is None:
+    if camera is not None and sh_rest is not None:
+        raise RuntimeError("camera_grads: not supported with split SH rows (sh_split=)")
+    if _EXT is not None and not want_all and means3D.is_cuda and aux_grads is None and camera is None:
         return _EXT.backward(background, means3D, radii, colors, scales, rotations, float(scale_modifier),
                              cov3D_precomp, viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color,
                              sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, bool(debug),
@@ -475,6 +481,9 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
         else:
             outs[n] = None
     ret = tuple(outs[n] for n in GRAD_NAMES)
+    if camera is not None:  # written by the finishing kernel, structural zeros included (P == 0: no launch)
+        cam_out = (torch.zeros if P == 0 else torch.empty)((35,), **f32)
+        ret += ((cam_out[:16].view(4, 4), cam_out[16:32].view(4, 4), cam_out[32:] if camera else None),)
     if P == 0:
         return ret
     dpix = _f32(dL_dout_color, "dL_dout_color", dev)
@@ -509,6 +518,15 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
                 rc = _lib.gs_backward_accumulate(*head, *x.scene(scale_modifier, x.colors), *bufs, _ptr(grad_scratch),
                                                  *grads, *tail)
         _native.check(rc, what)
+        if camera is not None:
+            cam_scratch = torch.empty((_lib.gs_camera_grad_scratch_bytes(P),), dtype=torch.uint8, device=dev)
+            rc = _lib.gs_backward_camera(*head, *x.scene(scale_modifier, x.colors), *x.camera(tan_fovx, tan_fovy),
+                                         _ptr(geomBuffer), int(R), _ptr(grad_scratch) if aux_grads is not None else None,
+                                         int(aux_grads is not None), _ptr(cam_scratch), _ptr(cam_out),
+                                         ctypes.c_void_p(cam_out.data_ptr() + 64),
+                                         ctypes.c_void_p(cam_out.data_ptr() + 128) if camera else None,
+                                         int(bool(debug)), st)
+            _native.check(rc, "rasterize_gaussians_backward (camera gradients)")
     return ret
 
 

@@ -11,6 +11,8 @@ Public surface used by the reference's render adapter
         -> (color [3, H, W] fp32, radii [P] int32)
     GaussianRasterizer(raster_settings)(..., aux_outputs=True)      (extension)
         -> (color, radii, invdepth [1, H, W] fp32, alpha [1, H, W] fp32)
+    GaussianRasterizer(raster_settings)(..., camera_grads=True)     (extension)
+        -> the same outputs; settings.viewmatrix / .projmatrix / .campos receive gradients
     GaussianRasterizer.markVisible(positions) -> bool [P]
     rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings)
@@ -347,11 +349,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                 st.wait_event(e)
             wait = evs[0] if evs else None
 
-        def _bwd(*a):
-            return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest)
+        cam = getattr(ctx, "camera", None)  # _RasterizeGaussiansCamera: the camera gradients behind this backward
 
+        def _bwd(*a):
+            return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
+                                    camera=cam)
+
+        res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+        if cam is not None:
+            ctx.camera_grads = res[8]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+         grad_rotations) = res[:8]
         for o in owners:
             if hasattr(o, "written"):
                 o.written(st)
@@ -461,12 +469,17 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                 st.wait_event(e)
             wait = evs[0] if evs else None
 
+        cam = getattr(ctx, "camera", None)  # as in _RasterizeGaussians.backward
+
         def _bwd(*a):
             return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
-                                    aux_grads=(grad_invdepth, grad_alpha))
+                                    aux_grads=(grad_invdepth, grad_alpha), camera=cam)
 
+        res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+        if cam is not None:
+            ctx.camera_grads = res[8]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+         grad_rotations) = res[:8]
         for o in owners:
             if hasattr(o, "written"):
                 o.written(st)
@@ -475,6 +488,49 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
         for k in sunk:
             grads[k] = None
         return tuple(grads)
+
+
+# ------------------------------------------------------------------------------------------
+# Camera gradients (an extension beyond the upstream API).  camera_grads=True: those of
+# settings.viewmatrix, .projmatrix and .campos that require grad enter the autograd Function as
+# tensor inputs and receive dL/dviewmatrix, dL/dprojmatrix [4, 4] and dL/dcampos [3], treated as
+# independent inputs (the caller's graph chains them to a pose: full_proj = view @ P, campos =
+# view.inverse()[3, :3]).  The forward, the Gaussian gradients and their kernels are those of the
+# plain / aux call, bit for bit; the backward goes over ctypes and gs_backward_camera follows it on
+# the stream (two small kernels: fp64 sums in a fixed order, bitwise reproducible).  Prepared views,
+# bounded forwards, split SH rows and deferring gradient owners are refused.
+# ------------------------------------------------------------------------------------------
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                viewmatrix, projmatrix, campos, raster_settings, aux):
+        # (viewmatrix, projmatrix, campos are raster_settings' own tensors: inputs for the graph's sake)
+        ctx.camera_aux = aux
+        ctx.camera_meta = tuple((t.shape, t.device) for t in (viewmatrix, projmatrix, campos))
+        if aux:
+            return _RasterizeGaussiansAux.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
+                                                  rotations, cov3Ds_precomp, raster_settings)
+        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                           cov3Ds_precomp, raster_settings)
+
+    @staticmethod
+    def backward(ctx, *grad_outs):
+        if _deferring_owner(ctx) is not None:
+            raise RuntimeError("camera_grads: not supported with a deferring gradient owner "
+                               "(GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
+        ctx.camera = bool(ctx.needs_input_grad[10])
+        ctx.camera_grads = None
+        if ctx.camera_aux:
+            grads = _RasterizeGaussiansAux.backward(ctx, *grad_outs)[:8]
+        else:
+            grads = _RasterizeGaussians.backward(ctx, *grad_outs)[:8]
+        cam = [None, None, None]
+        if ctx.camera_grads is not None:
+            for k, g in enumerate(ctx.camera_grads):
+                shape, device = ctx.camera_meta[k]
+                if g is not None and ctx.needs_input_grad[8 + k]:
+                    cam[k] = g.reshape(shape).to(device)
+        return tuple(grads) + tuple(cam) + (None, None)
 
 
 def _deferring_owner(ctx):
@@ -503,7 +559,8 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, prepared=None, sh_split=None, binning_capacity=None, aux_outputs=False):
+                cov3D_precomp=None, prepared=None, sh_split=None, binning_capacity=None, aux_outputs=False,
+                camera_grads=False):
         """prepared: this call's PreparedView from prepare_views (extension; default: none).
         binning_capacity: size the binning buffer for that many instances and run the forward
         without a host wait (extension, ABI v10; see bounded_status()).
@@ -513,8 +570,17 @@ class GaussianRasterizer(nn.Module):
         (what FusedAdam.step_activated consumes).  Bit-identical to passing the concatenation.
         aux_outputs: also return the expected inverse depth and the accumulated opacity of the same
         walk, (color, radii, invdepth [1,H,W], alpha [1,H,W]), both differentiable (extension; not
-        with prepared= or binning_capacity=)."""
+        with prepared= or binning_capacity=).
+        camera_grads: settings.viewmatrix / .projmatrix / .campos that require grad receive their
+        gradients (extension; with or without aux_outputs; not with prepared=, binning_capacity=,
+        sh_split= or a deferring gradient owner).  None of them requiring grad: the call without it."""
         s = self.raster_settings
+        if camera_grads:
+            for name, v in (("prepared", prepared), ("binning_capacity", binning_capacity), ("sh_split", sh_split)):
+                if v is not None:
+                    raise RuntimeError(f"camera_grads: not supported with {name}=")
+            camera_grads = any(isinstance(t, torch.Tensor) and t.requires_grad
+                               for t in (s.viewmatrix, s.projmatrix, s.campos))
         if aux_outputs and prepared is not None:
             raise RuntimeError("aux_outputs: not supported with prepared views (prepared=)")
         if aux_outputs and binning_capacity is not None:
@@ -530,6 +596,10 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        if camera_grads:
+            return _RasterizeGaussiansCamera.apply(means3D, means2D, shs, colors_precomp, opacities, scales,
+                                                   rotations, cov3D_precomp, s.viewmatrix, s.projmatrix, s.campos, s,
+                                                   bool(aux_outputs))
         if aux_outputs:
             return rasterize_gaussians_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                            cov3D_precomp, s, sh_split)

@@ -154,6 +154,13 @@ SIGNATURES = {
          _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
          _c_p, ctypes.c_uint, _c_p, _c_i, _c_p],
     ),
+    # GSRAST_HAS_CAMERA_GRAD: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos of one view after its backward
+    "gs_camera_grad_scratch_bytes": (_c_sz, [_c_i]),
+    "gs_backward_camera": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_f, _c_f, _c_p, _c_ll, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p],
+    ),
     # GSRAST_HAS_SKY: the skysphere background and its gradients
     "gs_sky_scratch_bytes": (_c_sz, [_c_i, _c_i]),
     "gs_sky_compose_forward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),

@@ -69,6 +69,9 @@ extern "C" {
  * gs_sky_compose_backward. */
 #define GSRAST_HAS_SKY 1
 
+/* Camera gradients (additive, same ABI version): gs_camera_grad_scratch_bytes, gs_backward_camera. */
+#define GSRAST_HAS_CAMERA_GRAD 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -80,6 +83,9 @@ size_t gs_grad_buffer_bytes(long long num_rendered);
 /* Grad scratch of gs_backward_accumulate_aux: the records of gs_grad_buffer_bytes(num_rendered), then
  * one float per instance slot (dL/d(1/z) of the instance) and one float per Gaussian (their sums). */
 size_t gs_grad_buffer_bytes_aux(long long num_rendered, int P);
+/* Scratch of gs_backward_camera: one row of 28 doubles (the 27 sums and a zero) per 256 Gaussians,
+ * 224 * max(1, ceil(P / 256)) bytes. */
+size_t gs_camera_grad_scratch_bytes(int P);
 /* The instance count a binning buffer of `bytes` bytes is laid out for: the largest n with
  * gs_binning_buffer_bytes(n, W, H) <= bytes (every such n gives the same layout).  A buffer that
  * gs_forward_counted filled for `capacity` instances goes to the backward with this count in place
@@ -321,6 +327,36 @@ int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int
                                float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
                                float* dL_dsh, float* dL_dscales, float* dL_drotations, unsigned accumulate,
                                void* wait_event, int debug, void* stream);
+
+/* ---- camera gradients (GSRAST_HAS_CAMERA_GRAD, an extension beyond upstream) ----
+ * dL/dviewmatrix [16], dL/dprojmatrix [16] and dL/dcampos [3] of one view, in the layout of the inputs
+ * (row-vector convention, v[4 r + c]).  Call it on the same stream right after a gs_backward,
+ * gs_backward_accumulate, _accumulate_aux or _accumulate_split of the same view, with that call's
+ * scene, camera, geom_buffer and num_rendered: it reads the per-Gaussian record sums that call left
+ * in the geometry buffer.  aux_grad_buffer / aux_valid: the grad_buffer of a gs_backward_accumulate_aux
+ * whose aux gradients were not both NULL, and 1; otherwise NULL / 0 (the inverse-depth sums are then
+ * not read).  scratch >= gs_camera_grad_scratch_bytes(P), 16-byte aligned, the caller's until the
+ * stream has passed this call.
+ *   dL/dview[r][k], k < 3: sum_i ph_r dL/dt_k + (r < 3) (J[0][k] dT0[r] + J[1][k] dT1[r]), ph = (mean, 1),
+ *     t = ph view, T = J W: the adjoints of the cov2D and clamp rules of the backward (a clamped tx / ty
+ *     is a constant, upstream's rule), plus ph_r (-s9 / z^2) for k = 2 with aux_valid; column 3 is 0.
+ *   dL/dproj[r][c]: the NDC mean's gradient, columns 0, 1 and 3; column 2 is 0.
+ *   dL/dcampos: minus the sum of the SH colour's dL/dmean term; 0 with colors_precomp.  dL_dcampos may
+ *     be NULL (the SH rows are then not read; after an _accumulate_split, whose rows are two tensors,
+ *     pass the concatenated rows as shs or NULL here).
+ * The three are treated as independent inputs (the caller chains them to a pose); tan_fovx / tan_fovy
+ * and the background get no gradient.  The sums run over the Gaussians with instances, in fp64 in a
+ * fixed order without atomics: bitwise reproducible.  The outputs are written, not accumulated;
+ * P == 0 writes zeros, and so does a view whose forward reported an invalid instance list.  Validation
+ * (the scene / camera checks of gs_backward, then the pointers) comes before any device work. */
+int gs_backward_camera(int P, int D, int M, const float* background, int image_width, int image_height,
+                       const float* means3D, const float* shs, const float* colors_precomp,
+                       const float* opacities, const float* scales, float scale_modifier,
+                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                       const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                       const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
+                       int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
+                       float* dL_dcampos, int debug, void* stream);
 
 /* ---- split SH rows (ABI v8, an extension beyond upstream) ----
  * render() concatenates GaussianModel's features_dc [P,1,3] and features_rest [P,M-1,3] into shs
