@@ -209,6 +209,14 @@ long long capacity_for(long long est) {
   return std::min<long long>(cap, (1ll << 31) - 1);
 }
 
+// upstream: nothing is launched for an empty scene; the image stays all-zero (no background)
+py::tuple empty_forward(int64_t H, int64_t W, const c10::Device& dev) {
+  const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
+  const auto f32o = at::TensorOptions().dtype(at::kFloat).device(dev);
+  return py::make_tuple(0, at::zeros({3, H, W}, f32o), at::zeros({0}, f32o.dtype(at::kInt)), at::empty({0}, u8),
+                        at::empty({0}, u8), at::empty({0}, u8));
+}
+
 // _C.rasterize_gaussians (no prepared view, no capacity): both halves of the forward
 py::tuple forward(const at::Tensor& background, const at::Tensor& means3D, const c10::optional<at::Tensor>& colors,
                   const c10::optional<at::Tensor>& opacity, const c10::optional<at::Tensor>& scales,
@@ -221,11 +229,7 @@ py::tuple forward(const at::Tensor& background, const at::Tensor& means3D, const
            sh_rest);
   const auto u8 = at::TensorOptions().dtype(at::kByte).device(x.dev);
   const auto f32o = at::TensorOptions().dtype(at::kFloat).device(x.dev);
-  if (x.P == 0) {
-    // upstream: nothing is launched for an empty scene; the image stays all-zero (no background)
-    return py::make_tuple(0, at::zeros({3, H, W}, f32o), at::zeros({0}, f32o.dtype(at::kInt)), at::empty({0}, u8),
-                          at::empty({0}, u8), at::empty({0}, u8));
-  }
+  if (x.P == 0) return empty_forward(H, W, x.dev);
   c10::DeviceGuard guard(x.dev);
   void* st = stream_of(x.dev);
   at::Tensor out_color = at::empty({3, H, W}, f32o);
@@ -278,10 +282,7 @@ py::tuple forward_bounded(const at::Tensor& background, const at::Tensor& means3
            sh_rest);
   const auto u8 = at::TensorOptions().dtype(at::kByte).device(x.dev);
   const auto f32o = at::TensorOptions().dtype(at::kFloat).device(x.dev);
-  if (x.P == 0) {
-    return py::make_tuple(0, at::zeros({3, H, W}, f32o), at::zeros({0}, f32o.dtype(at::kInt)), at::empty({0}, u8),
-                          at::empty({0}, u8), at::empty({0}, u8));
-  }
+  if (x.P == 0) return empty_forward(H, W, x.dev);
   c10::DeviceGuard guard(x.dev);
   at::Tensor out_color = at::empty({3, H, W}, f32o);
   at::Tensor radii = at::empty({x.P}, f32o.dtype(at::kInt));
@@ -444,6 +445,7 @@ py::list preprocess_views(const std::vector<at::Tensor>& backgrounds, const at::
     vst[k] = streams.empty() ? nullptr : reinterpret_cast<void*>(streams[k]);
   }
   const bool bounded = capacities.has_value();
+  // (two call sites: the entries' types differ, the bounded one reads nr through a const pointer)
   if (bounded) {
     for (int k = 0; k < K; k++) nr[k] = (*capacities)[k];
     check(F.pre_views_bounded(K, (int)x.P, (int)degree, (int)x.M, bgp, wv, hv, fp(x.means3D), fp(x.sh), fp(x.colors),
@@ -464,6 +466,7 @@ py::list preprocess_views(const std::vector<at::Tensor>& backgrounds, const at::
     return !(e && e[0] == '0' && e[1] == 0);
   }();
   std::vector<py::tuple> tuples;
+  std::vector<at::Tensor> bins, imgs;  // with the batched binning: every view's buffers
   if (batch && same_size) {
     // the K views' binning as one set of launches: every binning buffer a slice of one allocation,
     // sized for the largest count, which then stands for every view's num_rendered
@@ -472,7 +475,7 @@ py::list preprocess_views(const std::vector<at::Tensor>& backgrounds, const at::
     const int64_t bb = (int64_t)F.binning_bytes(I, wv[0], hv[0]), ib = (int64_t)F.image_bytes(wv[0], hv[0]);
     at::Tensor bin_all = at::empty({K * bb}, u8), img_all = at::empty({K * ib}, u8);
     void *bp[8], *ip[8];
-    std::vector<at::Tensor> bins(K), imgs(K);
+    bins.resize(K), imgs.resize(K);
     for (int k = 0; k < K; k++) {
       bins[k] = bin_all.narrow(0, k * bb, bb), imgs[k] = img_all.narrow(0, k * ib, ib);
       bp[k] = bins[k].data_ptr(), ip[k] = imgs[k].data_ptr();
@@ -480,23 +483,17 @@ py::list preprocess_views(const std::vector<at::Tensor>& backgrounds, const at::
     check(F.bin_views(K, (int)x.P, wv[0], hv[0], gp, nr, bp, ip, (int)debug, st, streams.empty() ? nullptr : vst),
           "preprocess_views (binning)");
     for (int k = 0; k < K; k++) tuples.push_back(py::make_tuple((int64_t)I, radii[k], geoms[k], bounded, bins[k], imgs[k]));
-    if (!streams.empty())
-      for (int k = 0; k < K; k++) {
-        // (torch on ROCm keys its HIP streams as CUDA streams)
-        const c10::Stream sk =
-            at::hip::getStreamFromExternalMasqueradingAsCUDA((hipStream_t)vst[k], x.dev.index()).unwrap();
-        radii[k].record_stream(sk), geoms[k].record_stream(sk), bins[k].record_stream(sk), imgs[k].record_stream(sk);
-      }
   } else {
     for (int k = 0; k < K; k++) tuples.push_back(py::make_tuple((int64_t)nr[k], radii[k], geoms[k], bounded));
-    if (!streams.empty())
-      for (int k = 0; k < K; k++) {
-        // (torch on ROCm keys its HIP streams as CUDA streams)
-        const c10::Stream sk =
-            at::hip::getStreamFromExternalMasqueradingAsCUDA((hipStream_t)vst[k], x.dev.index()).unwrap();
-        radii[k].record_stream(sk), geoms[k].record_stream(sk);
-      }
   }
+  if (!streams.empty())  // the buffers are used on the views' streams
+    for (int k = 0; k < K; k++) {
+      // (torch on ROCm keys its HIP streams as CUDA streams)
+      const c10::Stream sk =
+          at::hip::getStreamFromExternalMasqueradingAsCUDA((hipStream_t)vst[k], x.dev.index()).unwrap();
+      radii[k].record_stream(sk), geoms[k].record_stream(sk);
+      if (!bins.empty()) bins[k].record_stream(sk), imgs[k].record_stream(sk);
+    }
   for (auto& t : tuples) out.append(t);
   return out;
 }
@@ -514,9 +511,7 @@ py::tuple forward_prepared(const at::Tensor& background, const at::Tensor& means
   const long long nr = prepared[0].cast<long long>();
   at::Tensor radii = prepared[1].cast<at::Tensor>(), geom = prepared[2].cast<at::Tensor>();
   const bool bounded = prepared.size() > 3 && prepared[3].cast<bool>();
-  if (P == 0)
-    return py::make_tuple(0, at::zeros({3, H, W}, f32o), at::zeros({0}, f32o.dtype(at::kInt)), at::empty({0}, u8),
-                          at::empty({0}, u8), at::empty({0}, u8));
+  if (P == 0) return empty_forward(H, W, dev);
   TORCH_CHECK(radii.numel() == P && geom.numel() == (int64_t)F.geom_bytes((int)P),
               "rasterize_gaussians: the prepared view does not match these inputs");
   at::Tensor bg = f32(background, "background", dev, true), view = f32(viewmatrix, "viewmatrix", dev, true);

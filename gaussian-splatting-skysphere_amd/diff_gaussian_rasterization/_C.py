@@ -70,6 +70,13 @@ def _f32(t, name, device, allow_empty=True, host_ok=False):
     return t.contiguous()
 
 
+def _camera_side(device, background, viewmatrix, projmatrix, campos):
+    """(bg, view, proj, campos) of a call that takes them outside _Inputs: the camera-side tensors
+    may come from the host (_f32(..., host_ok=True)); an absent one stays None."""
+    return (_f32(background, "background", device, host_ok=True), _f32(viewmatrix, "viewmatrix", device, host_ok=True),
+            _f32(projmatrix, "projmatrix", device, host_ok=True), _f32(campos, "campos", device, host_ok=True))
+
+
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
@@ -312,16 +319,25 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         raise RuntimeError("split SH rows are not supported with prepared views")
     if prepared is not None and capacity is not None:
         raise RuntimeError("a binning capacity is not supported with prepared views")
-    H, W = int(image_height), int(image_width)
+    return _forward_ctypes(x, int(image_height), int(image_width), degree, scale_modifier, tan_fovx, tan_fovy,
+                           prefiltered, debug, prepared=prepared, capacity=capacity)
+
+
+def _forward_ctypes(x, H, W, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug, prepared=None,
+                    capacity=None, aux=False):
+    """The forward of validated inputs over ctypes: rasterize_gaussians' six values, and with aux
+    (the two-call path only) the render's (invdepth [1, H, W], alpha [1, H, W]) behind them."""
     dev = x.device
     u8 = dict(dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
     if x.P == 0:
-        # upstream: nothing is launched for an empty scene; the image stays all-zero (no background)
-        return (0, torch.zeros((3, H, W), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.int32,
-                                                                                        device=dev),
-                torch.empty((0,), **u8), torch.empty((0,), **u8), torch.empty((0,), **u8))
-    # every pixel of the image and every radius is written by the kernels
-    out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        # upstream: nothing is launched for an empty scene; the images stay all-zero (no background)
+        return (0, torch.zeros((3, H, W), **f32), torch.zeros((0,), dtype=torch.int32, device=dev),
+                torch.empty((0,), **u8), torch.empty((0,), **u8), torch.empty((0,), **u8)) + tuple(
+                    torch.zeros((1, H, W), **f32) for _ in range(2 if aux else 0))
+    # every pixel of the images and every radius is written by the kernels
+    out_color = torch.empty((3, H, W), **f32)
+    planes = tuple(torch.empty((1, H, W), **f32) for _ in range(2 if aux else 0))  # invdepth, alpha
     if capacity is not None:
         capacity = int(capacity)
         radii = torch.empty((x.P,), dtype=torch.int32, device=dev)
@@ -359,12 +375,16 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                                                      debug, st)
         binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
+        if aux:
+            render, what = _lib.gs_forward_render_aux, "rasterize_gaussians (render, aux outputs)"
+        else:
+            render = _lib.gs_forward_render_bounded if bounded else _lib.gs_forward_render
+            what = "rasterize_gaussians (render)"
         _native.check(
-            (_lib.gs_forward_render_bounded if bounded else _lib.gs_forward_render)(
-                x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(radii), _ptr(geom), num_rendered,
-                _ptr(binning), _ptr(img), _ptr(out_color), int(bool(debug)), st),
-            "rasterize_gaussians (render)")
-    return num_rendered, out_color, radii, geom, binning, img
+            render(x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(radii), _ptr(geom), num_rendered,
+                   _ptr(binning), _ptr(img), _ptr(out_color), *map(_ptr, planes), int(bool(debug)), st),
+            what)
+    return (num_rendered, out_color, radii, geom, binning, img) + planes
 
 
 def rasterize_gaussians_aux(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -374,29 +394,8 @@ def rasterize_gaussians_aux(background, means3D, colors, opacity, scales, rotati
     values and (invdepth [1, H, W], alpha [1, H, W]).  Always the two-call path over ctypes."""
     x = _Inputs(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
                 campos, sh_rest=sh_rest)
-    H, W = int(image_height), int(image_width)
-    dev = x.device
-    u8 = dict(dtype=torch.uint8, device=dev)
-    f32 = dict(dtype=torch.float32, device=dev)
-    if x.P == 0:  # nothing is launched for an empty scene: all-zero outputs
-        return (0, torch.zeros((3, H, W), **f32), torch.zeros((0,), dtype=torch.int32, device=dev),
-                torch.empty((0,), **u8), torch.empty((0,), **u8), torch.empty((0,), **u8),
-                torch.zeros((1, H, W), **f32), torch.zeros((1, H, W), **f32))
-    # every pixel of the three images and every radius is written by the kernels
-    out_color = torch.empty((3, H, W), **f32)
-    invdepth, alpha = torch.empty((1, H, W), **f32), torch.empty((1, H, W), **f32)
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        num_rendered, radii, geom = x.preprocess(W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug,
-                                                 st)
-        binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
-        img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
-        _native.check(
-            _lib.gs_forward_render_aux(
-                x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(radii), _ptr(geom), num_rendered,
-                _ptr(binning), _ptr(img), _ptr(out_color), _ptr(invdepth), _ptr(alpha), int(bool(debug)), st),
-            "rasterize_gaussians (render, aux outputs)")
-    return num_rendered, out_color, radii, geom, binning, img, invdepth, alpha
+    return _forward_ctypes(x, int(image_height), int(image_width), degree, scale_modifier, tan_fovx, tan_fovy,
+                           prefiltered, debug, aux=True)
 
 
 def binning_layout_count(R, binningBuffer, W, H):
@@ -543,10 +542,7 @@ def backward_render(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fo
     dm2 = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_means2D else None
     if P == 0:
         return dm2
-    bg = _f32(background, "background", dev, host_ok=True)
-    view = _f32(viewmatrix, "viewmatrix", dev, host_ok=True)
-    proj = _f32(projmatrix, "projmatrix", dev, host_ok=True)
-    cam = _f32(campos, "campos", dev, host_ok=True)
+    bg, view, proj, cam = _camera_side(dev, background, viewmatrix, projmatrix, campos)
     dpix = _f32(dL_dout_color, "dL_dout_color", dev)
     R = binning_layout_count(R, binningBuffer, W, H)
     with torch.cuda.device(dev):
@@ -581,8 +577,7 @@ def backward_gaussians(means3D, sh, colors, scales, rotations, cov3D_precomp, sc
     arr = (_native.ViewGrad * len(views))()
     keep = []
     for k, (vm, pm, cp, tx, ty, W, H, geom) in enumerate(views):
-        vm, pm = _f32(vm, "viewmatrix", dev, host_ok=True), _f32(pm, "projmatrix", dev, host_ok=True)
-        cp = _f32(cp, "campos", dev, host_ok=True)
+        _, vm, pm, cp = _camera_side(dev, None, vm, pm, cp)
         keep += [vm, pm, cp]
         arr[k] = _native.ViewGrad(vm.data_ptr(), pm.data_ptr(), cp.data_ptr() if cp is not None else None,
                                   float(tx), float(ty), int(W), int(H), geom.data_ptr())
@@ -621,8 +616,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     if P == 0:
         return present
     m = _f32(means3D, "means3D", dev)
-    v = _f32(viewmatrix, "viewmatrix", dev, host_ok=True)
-    p = _f32(projmatrix, "projmatrix", dev, host_ok=True)
+    _, v, p, _ = _camera_side(dev, None, viewmatrix, projmatrix, None)
     with torch.cuda.device(dev):
         _native.check(_lib.gs_mark_visible(P, _ptr(m), _ptr(v), _ptr(p), _ptr(present), _stream(dev)), "mark_visible")
     return present

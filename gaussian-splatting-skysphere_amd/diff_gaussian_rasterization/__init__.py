@@ -49,10 +49,31 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
 # holds one, ADDED (gs_backward_accumulate) -- straight into the buffer its owner hands out
 # (normally the tensor's own .grad, a view into a flat all-reduce bucket), and the autograd
 # Function returns None for it.  The result equals autograd's `grad += g` with no extra pass over
-# the gradients and no pack/unpack copy.  owner.claim(tensor) -> (buffer, accumulate) or None
-# (None: the normal autograd path).  Optional: owner.write_order(stream) -> torch.cuda.Event or None
-# (the stream waits for it before the gradient-writing kernel) and owner.written(stream), called
-# once the backward is enqueued -- an owner shared by views on several streams orders its writes.
+# the gradients and no pack/unpack copy.
+#
+# The owner protocol (duck-typed, no base class; gs_view_parallel.GradBucket and
+# gs_train_step._AdamBackward are the owners in the tree).  Required:
+#   owner.claim(tensor) -> (buffer, accumulate) or None     None: the normal autograd path.  Asked in
+#       the backward, in input order, for each registered input that needs a gradient.
+# Optional hooks, each looked up in one place (_forward_step, _backward_step, _deferring_owner):
+#   owner.forwarded(geomBuffer, P)     after the forward, once per distinct owner of the call's sinks:
+#       the view's geometry buffer, whose error-flags word can be copied out behind the forward.
+#   owner.write_order(stream) -> torch.cuda.Event or None   the stream waits for it before the
+#       gradient-writing kernel; owner.written(stream) is called once the backward is enqueued.  An
+#       owner shared by views on several streams orders its writes with the two; only owners whose
+#       claim handed out a buffer are asked.
+#   owner.defers (a true attribute) and owner.defer_view(ctx, inputs, view)   the owner of the call's
+#       first sink takes the whole per-Gaussian half of a plain backward when every input gradient
+#       the backward must produce (means2D aside) is registered with it: only the per-tile half runs
+#       (_C.backward_render, dL/dmeans2D returned to autograd), nothing is claimed, and defer_view
+#       gets inputs = dict(means3D, sh, colors, scales, rotations, cov3D, scale_modifier, degree,
+#       debug, sh_rest) and view = (viewmatrix, projmatrix, campos, tanfovx, tanfovy, W, H,
+#       geomBuffer) for _C.backward_gaussians.  Aux gradients and camera gradients refuse such an owner.
+#   owner.accepts_sh_split (a true attribute)   a deferring owner that handles split SH rows
+#       (inputs["sh_rest"]); without it a deferred sh_split view is refused.
+# What an owner may read from the `ctx` it is handed: ctx.sinks, the call's registered inputs that
+# require grad as [(input index, gradient name, tensor, owner)] in _SINK_INPUTS order, and
+# ctx.needs_input_grad[0:8], the same eight inputs in every Function.  Nothing else of ctx is stable.
 # ------------------------------------------------------------------------------------------
 _SINKS: dict = {}  # id(tensor) -> (weakref to the tensor, owner)
 
@@ -231,143 +252,163 @@ def _run_with_snapshot(fn, args, debug, dump_name, phase):
         raise
 
 
+def _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s,
+                  prepared=None, sh_split=None, binning_capacity=None, aux=False):
+    """The forward of the three autograd Functions: the native call (plain, with split SH rows or a
+    binning capacity, over a prepared view, or with the aux outputs), everything the backward needs
+    on `ctx`, and the call's gradient sinks.  -> (color, radii), or with aux (color, radii, invdepth,
+    alpha)."""
+    # the camera matrices arrive transposed (cameras.py:54-56 world_view_transform is a
+    # .transpose(0, 1) view); make them contiguous once and reuse them in backward
+    view, proj = _contiguous_matrix(s.viewmatrix), _contiguous_matrix(s.projmatrix)
+    sh_rest = None
+    sh_input = sh  # the autograd input (with sh_split: the gradient carrier; its sink owner receives dL/dshs)
+    if sh_split is not None:
+        # split SH rows: the kernels read features_dc / features_rest in place; `sh` is only the
+        # [P, M, 3] carrier of the concatenation's gradient (its values are never read)
+        dc, sh_rest = (t.detach() for t in sh_split)
+        if prepared is not None:
+            raise RuntimeError("sh_split: not supported with prepared views")
+        if tuple(sh.shape) != (dc.shape[0], 1 + sh_rest.shape[1], 3):
+            raise RuntimeError("sh_split: shs must be the [P, M, 3] gradient carrier of cat(features_dc, "
+                               "features_rest)")
+        sh = dc
+    args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            view, proj, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
+            s.campos, s.prefiltered, s.debug)
+    if prepared is not None and binning_capacity is not None:
+        raise RuntimeError("binning_capacity: not supported with prepared views")
+    if prepared is not None:
+        nz = lambda t: None if t is None or t.numel() == 0 else t  # noqa: E731
+        tri = prepared.take(s, (means3D, nz(sh), nz(colors_precomp), opacities, nz(scales), nz(rotations),
+                                nz(cov3Ds_precomp)))
+        out = _C.rasterize_gaussians(*args, prepared=tri)
+    else:
+        if aux:
+            fn = lambda *a: _C.rasterize_gaussians_aux(*a, sh_rest=sh_rest)  # noqa: E731
+        elif sh_rest is not None or binning_capacity is not None:
+            fn = lambda *a: _C.rasterize_gaussians(*a, sh_rest=sh_rest, capacity=binning_capacity)  # noqa: E731
+        else:
+            fn = _C.rasterize_gaussians
+        out = _run_with_snapshot(fn, args, s.debug, "snapshot_fw.dump", "forward")
+    num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = out[:6]
+    ctx.raster_settings = s
+    ctx.num_rendered = num_rendered
+    ctx.matrices = (view, proj)
+    ctx.sh_rest = sh_rest
+    # the split rows are kept outside save_for_backward (they are not inputs of the Function):
+    # their version counters stand in for autograd's in-place check
+    ctx.sh_split_versions = None if sh_rest is None else (sh._version, sh_rest._version)
+    ctx.set_materialize_grads(False)  # no zero-filled gradient for the (int) radii output, or an unused one
+    ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
+                          binningBuffer, imgBuffer)
+    ctx.mark_non_differentiable(radii)
+    sinks = []
+    if _SINKS:
+        inputs = (means3D, means2D, sh_input, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        for k, name in _SINK_INPUTS:
+            owner = _sink_owner(inputs[k])
+            if owner is not None:
+                sinks.append((k, name, inputs[k], owner))
+        # an owner that follows its views' forward status (gs_train_step._AdamBackward) gets the
+        # view's geometry buffer now, while its error-flags word can still be copied out
+        # stream-ordered behind this forward
+        for owner in {id(o): o for _k, _n, _t, o in sinks}.values():
+            if hasattr(owner, "forwarded"):
+                owner.forwarded(geomBuffer, means3D.shape[0])
+    ctx.sinks = sinks
+    return (color, radii) + tuple(out[6:])
+
+
+def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
+    """The backward of the three autograd Functions.  aux_grads: None or (dL/dinvdepth, dL/dalpha),
+    either may be None; camera: None, or whether dL/dcampos is wanted.  -> (the eight Gaussian
+    gradients in input order, None where an owner's buffer or a deferred pass received it; the
+    camera gradients (dL/dviewmatrix, dL/dprojmatrix, dL/dcampos or None), or None without `camera`
+    or when no output reached the loss).  A deferring owner takes the view here; the callers that
+    cannot be deferred (aux gradients, camera gradients) refuse it first."""
+    if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
+        aux_grads = None  # only the colour reached the loss (or nothing did): the plain backward
+    if grad_out_color is None and aux_grads is None:  # no output reached the loss
+        return (None,) * 8, None
+    s = ctx.raster_settings
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = (
+        ctx.saved_tensors)
+    if ctx.sh_rest is not None and (sh._version, ctx.sh_rest._version) != ctx.sh_split_versions:
+        raise RuntimeError("sh_split: features_dc or features_rest was modified by an inplace operation between "
+                           "the forward and the backward")
+    view, proj = ctx.matrices
+    if grad_out_color is None:  # the loss reads the aux outputs only
+        grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
+    args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            view, proj, s.tanfovx, s.tanfovy, grad_out_color.contiguous(), sh, s.sh_degree,
+            s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
+
+    # a sink owner that defers the per-Gaussian half (GradBucket(defer=True)) takes this view
+    # when every parameter gradient the call needs goes to it: only the per-tile half and
+    # dL_dmeans2D run now, the per-Gaussian half later for all of its views in one pass
+    deferrer = _deferring_owner(ctx)
+    if deferrer is not None and ctx.sh_rest is not None and not getattr(deferrer, "accepts_sh_split", False):
+        raise RuntimeError("sh_split: not supported with a deferring gradient bucket")
+    if deferrer is not None:
+        M = (1 + ctx.sh_rest.size(1)) if ctx.sh_rest is not None else (sh.size(1) if sh.ndimension() == 3 else 0)
+        dm2 = _C.backward_render(s.bg, view, proj, s.campos, s.tanfovx, s.tanfovy, grad_out_color.contiguous(),
+                                 means3D.size(0), s.sh_degree, M,
+                                 geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, ctx.needs_input_grad[1],
+                                 s.debug)
+        deferrer.defer_view(ctx, dict(means3D=means3D, sh=sh, colors=colors_precomp, scales=scales,
+                                      rotations=rotations, cov3D=cov3Ds_precomp, scale_modifier=s.scale_modifier,
+                                      degree=s.sh_degree, debug=s.debug, sh_rest=ctx.sh_rest),
+                            (view, proj, s.campos, s.tanfovx, s.tanfovy, s.image_width, s.image_height,
+                             geomBuffer))
+        return (None, dm2) + (None,) * 6, None
+
+    sinks, sunk, owners = {}, set(), []
+    for k, name, t, owner in ctx.sinks:
+        if ctx.needs_input_grad[k]:
+            claim = owner.claim(t)
+            if claim is not None:
+                sinks[name] = claim
+                sunk.add(k)
+                if all(o is not owner for o in owners):
+                    owners.append(owner)
+    # sink owners may order their buffer's writes across streams (views rendered on several
+    # streams, GradBucket): the last kernel waits for the owner's previous write
+    wait = None
+    if owners:
+        st = torch.cuda.current_stream(grad_out_color.device)
+        evs = [e for e in (o.write_order(st) for o in owners if hasattr(o, "write_order")) if e is not None]
+        for e in evs[1:]:
+            st.wait_event(e)
+        wait = evs[0] if evs else None
+
+    def _bwd(*a):
+        return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
+                                aux_grads=aux_grads, camera=camera)
+
+    res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+    (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+     grad_rotations) = res[:8]
+    for o in owners:
+        if hasattr(o, "written"):
+            o.written(st)
+    grads = [grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
+             grad_rotations, grad_cov3Ds_precomp]
+    for k in sunk:  # already in the sink's buffer (the tensor's .grad)
+        grads[k] = None
+    return tuple(grads), (res[8] if camera is not None else None)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, prepared=None, sh_split=None, binning_capacity=None):
-        s = raster_settings
-        # the camera matrices arrive transposed (cameras.py:54-56 world_view_transform is a
-        # .transpose(0, 1) view); make them contiguous once and reuse them in backward
-        view, proj = _contiguous_matrix(s.viewmatrix), _contiguous_matrix(s.projmatrix)
-        sh_rest = None
-        sh_input = sh  # the autograd input (with sh_split: the gradient carrier; its sink owner receives dL/dshs)
-        if sh_split is not None:
-            # split SH rows: the kernels read features_dc / features_rest in place; `sh` is only the
-            # [P, M, 3] carrier of the concatenation's gradient (its values are never read)
-            dc, sh_rest = (t.detach() for t in sh_split)
-            if prepared is not None:
-                raise RuntimeError("sh_split: not supported with prepared views")
-            if tuple(sh.shape) != (dc.shape[0], 1 + sh_rest.shape[1], 3):
-                raise RuntimeError("sh_split: shs must be the [P, M, 3] gradient carrier of cat(features_dc, "
-                                   "features_rest)")
-            sh = dc
-        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                view, proj, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug)
-        if prepared is not None and binning_capacity is not None:
-            raise RuntimeError("binning_capacity: not supported with prepared views")
-        if sh_rest is not None or binning_capacity is not None:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _run_with_snapshot(
-                lambda *a: _C.rasterize_gaussians(*a, sh_rest=sh_rest, capacity=binning_capacity), args, s.debug,
-                "snapshot_fw.dump", "forward")
-        elif prepared is not None:
-            nz = lambda t: None if t is None or t.numel() == 0 else t  # noqa: E731
-            tri = prepared.take(s, (means3D, nz(sh), nz(colors_precomp), opacities, nz(scales), nz(rotations),
-                                    nz(cov3Ds_precomp)))
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args,
-                                                                                                     prepared=tri)
-        else:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _run_with_snapshot(
-                _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        ctx.matrices = (view, proj)
-        ctx.sh_rest = sh_rest
-        # the split rows are kept outside save_for_backward (they are not inputs of the Function):
-        # their version counters stand in for autograd's in-place check
-        ctx.sh_split_versions = None if sh_rest is None else (sh._version, sh_rest._version)
-        ctx.set_materialize_grads(False)  # no zero-filled gradient for the (int) radii output
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
-        sinks = []
-        if _SINKS:
-            inputs = (means3D, means2D, sh_input, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-            for k, name in _SINK_INPUTS:
-                owner = _sink_owner(inputs[k])
-                if owner is not None:
-                    sinks.append((k, name, inputs[k], owner))
-            # an owner that follows its views' forward status (gs_train_step._AdamBackward) gets the
-            # view's geometry buffer now, while its error-flags word can still be copied out
-            # stream-ordered behind this forward
-            for owner in {id(o): o for _k, _n, _t, o in sinks}.values():
-                if hasattr(owner, "forwarded"):
-                    owner.forwarded(geomBuffer, means3D.shape[0])
-        ctx.sinks = sinks
-        return color, radii
+        return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                             raster_settings, prepared, sh_split, binning_capacity)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
-        s = ctx.raster_settings
-        if grad_out_color is None:  # the colour output did not reach the loss
-            return (None,) * 12
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = (
-            ctx.saved_tensors)
-        if ctx.sh_rest is not None and (sh._version, ctx.sh_rest._version) != ctx.sh_split_versions:
-            raise RuntimeError("sh_split: features_dc or features_rest was modified by an inplace operation between "
-                               "the forward and the backward")
-        view, proj = ctx.matrices
-        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                view, proj, s.tanfovx, s.tanfovy, grad_out_color.contiguous(), sh, s.sh_degree,
-                s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
-
-        # a sink owner that defers the per-Gaussian half (GradBucket(defer=True)) takes this view
-        # when every parameter gradient the call needs goes to it: only the per-tile half and
-        # dL_dmeans2D run now, the per-Gaussian half later for all of its views in one pass
-        deferrer = _deferring_owner(ctx)
-        if deferrer is not None and ctx.sh_rest is not None and not getattr(deferrer, "accepts_sh_split", False):
-            raise RuntimeError("sh_split: not supported with a deferring gradient bucket")
-        if deferrer is not None:
-            M = (1 + ctx.sh_rest.size(1)) if ctx.sh_rest is not None else (sh.size(1) if sh.ndimension() == 3 else 0)
-            dm2 = _C.backward_render(s.bg, view, proj, s.campos, s.tanfovx, s.tanfovy, grad_out_color.contiguous(),
-                                     means3D.size(0), s.sh_degree, M,
-                                     geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, ctx.needs_input_grad[1],
-                                     s.debug)
-            deferrer.defer_view(ctx, dict(means3D=means3D, sh=sh, colors=colors_precomp, scales=scales,
-                                          rotations=rotations, cov3D=cov3Ds_precomp, scale_modifier=s.scale_modifier,
-                                          degree=s.sh_degree, debug=s.debug, sh_rest=ctx.sh_rest),
-                                (view, proj, s.campos, s.tanfovx, s.tanfovy, s.image_width, s.image_height,
-                                 geomBuffer))
-            return (None, dm2) + (None,) * 10
-
-        sinks, sunk, owners = {}, set(), []
-        for k, name, t, owner in ctx.sinks:
-            if ctx.needs_input_grad[k]:
-                claim = owner.claim(t)
-                if claim is not None:
-                    sinks[name] = claim
-                    sunk.add(k)
-                    if all(o is not owner for o in owners):
-                        owners.append(owner)
-        # sink owners may order their buffer's writes across streams (views rendered on several
-        # streams, GradBucket): the last kernel waits for the owner's previous write
-        wait = None
-        if owners:
-            st = torch.cuda.current_stream(grad_out_color.device)
-            evs = [e for e in (o.write_order(st) for o in owners if hasattr(o, "write_order")) if e is not None]
-            for e in evs[1:]:
-                st.wait_event(e)
-            wait = evs[0] if evs else None
-
-        cam = getattr(ctx, "camera", None)  # _RasterizeGaussiansCamera: the camera gradients behind this backward
-
-        def _bwd(*a):
-            return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
-                                    camera=cam)
-
-        res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
-        if cam is not None:
-            ctx.camera_grads = res[8]
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = res[:8]
-        for o in owners:
-            if hasattr(o, "written"):
-                o.written(st)
-        grads = [grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                 grad_rotations, grad_cov3Ds_precomp, None, None, None, None]
-        for k in sunk:  # already in the sink's buffer (the tensor's .grad)
-            grads[k] = None
-        return tuple(grads)
+        return _backward_step(ctx, grad_out_color)[0] + (None,) * 4
 
 
 # ------------------------------------------------------------------------------------------
@@ -392,102 +433,16 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, sh_split=None):
-        s = raster_settings
-        view, proj = _contiguous_matrix(s.viewmatrix), _contiguous_matrix(s.projmatrix)
-        sh_rest = None
-        sh_input = sh
-        if sh_split is not None:  # as _RasterizeGaussians: `sh` is the gradient carrier only
-            dc, sh_rest = (t.detach() for t in sh_split)
-            if tuple(sh.shape) != (dc.shape[0], 1 + sh_rest.shape[1], 3):
-                raise RuntimeError("sh_split: shs must be the [P, M, 3] gradient carrier of cat(features_dc, "
-                                   "features_rest)")
-            sh = dc
-        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                view, proj, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug)
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, invdepth, alpha = _run_with_snapshot(
-            lambda *a: _C.rasterize_gaussians_aux(*a, sh_rest=sh_rest), args, s.debug, "snapshot_fw.dump", "forward")
-        # the same context as _RasterizeGaussians: a backward without an aux gradient is its backward
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        ctx.matrices = (view, proj)
-        ctx.sh_rest = sh_rest
-        ctx.sh_split_versions = None if sh_rest is None else (sh._version, sh_rest._version)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
-        sinks = []
-        if _SINKS:
-            inputs = (means3D, means2D, sh_input, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-            for k, name in _SINK_INPUTS:
-                owner = _sink_owner(inputs[k])
-                if owner is not None:
-                    sinks.append((k, name, inputs[k], owner))
-            for owner in {id(o): o for _k, _n, _t, o in sinks}.values():
-                if hasattr(owner, "forwarded"):
-                    owner.forwarded(geomBuffer, means3D.shape[0])
-        ctx.sinks = sinks
-        return color, radii, invdepth, alpha
+        return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                             raster_settings, sh_split=sh_split, aux=True)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_invdepth, grad_alpha):
-        if grad_invdepth is None and grad_alpha is None:
-            # only the colour reached the loss (or nothing did): the plain backward, as it stands
-            return tuple(_RasterizeGaussians.backward(ctx, grad_out_color, None)[:8]) + (None, None)
-        s = ctx.raster_settings
-        if _deferring_owner(ctx) is not None:
+        # without an aux gradient the backward is the plain one, which a deferring owner may take
+        if (grad_invdepth is not None or grad_alpha is not None) and _deferring_owner(ctx) is not None:
             raise RuntimeError("aux_outputs: an alpha / inverse-depth gradient is not supported with a deferring "
                                "gradient owner (GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = (
-            ctx.saved_tensors)
-        if ctx.sh_rest is not None and (sh._version, ctx.sh_rest._version) != ctx.sh_split_versions:
-            raise RuntimeError("sh_split: features_dc or features_rest was modified by an inplace operation between "
-                               "the forward and the backward")
-        view, proj = ctx.matrices
-        if grad_out_color is None:  # the loss reads the aux outputs only
-            grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32,
-                                         device=means3D.device)
-        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                view, proj, s.tanfovx, s.tanfovy, grad_out_color.contiguous(), sh, s.sh_degree,
-                s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
-        # gradient sinks and their write order, as in _RasterizeGaussians.backward
-        sinks, sunk, owners = {}, set(), []
-        for k, name, t, owner in ctx.sinks:
-            if ctx.needs_input_grad[k]:
-                claim = owner.claim(t)
-                if claim is not None:
-                    sinks[name] = claim
-                    sunk.add(k)
-                    if all(o is not owner for o in owners):
-                        owners.append(owner)
-        wait = None
-        if owners:
-            st = torch.cuda.current_stream(grad_out_color.device)
-            evs = [e for e in (o.write_order(st) for o in owners if hasattr(o, "write_order")) if e is not None]
-            for e in evs[1:]:
-                st.wait_event(e)
-            wait = evs[0] if evs else None
-
-        cam = getattr(ctx, "camera", None)  # as in _RasterizeGaussians.backward
-
-        def _bwd(*a):
-            return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
-                                    aux_grads=(grad_invdepth, grad_alpha), camera=cam)
-
-        res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
-        if cam is not None:
-            ctx.camera_grads = res[8]
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = res[:8]
-        for o in owners:
-            if hasattr(o, "written"):
-                o.written(st)
-        grads = [grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                 grad_rotations, grad_cov3Ds_precomp, None, None]
-        for k in sunk:
-            grads[k] = None
-        return tuple(grads)
+        return _backward_step(ctx, grad_out_color, (grad_invdepth, grad_alpha))[0] + (None, None)
 
 
 # ------------------------------------------------------------------------------------------
@@ -507,30 +462,23 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
         # (viewmatrix, projmatrix, campos are raster_settings' own tensors: inputs for the graph's sake)
         ctx.camera_aux = aux
         ctx.camera_meta = tuple((t.shape, t.device) for t in (viewmatrix, projmatrix, campos))
-        if aux:
-            return _RasterizeGaussiansAux.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
-                                                  rotations, cov3Ds_precomp, raster_settings)
-        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                           cov3Ds_precomp, raster_settings)
+        return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                             raster_settings, aux=aux)
 
     @staticmethod
     def backward(ctx, *grad_outs):
         if _deferring_owner(ctx) is not None:
             raise RuntimeError("camera_grads: not supported with a deferring gradient owner "
                                "(GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
-        ctx.camera = bool(ctx.needs_input_grad[10])
-        ctx.camera_grads = None
-        if ctx.camera_aux:
-            grads = _RasterizeGaussiansAux.backward(ctx, *grad_outs)[:8]
-        else:
-            grads = _RasterizeGaussians.backward(ctx, *grad_outs)[:8]
+        grads, camera_grads = _backward_step(ctx, grad_outs[0], grad_outs[2:4] if ctx.camera_aux else None,
+                                             bool(ctx.needs_input_grad[10]))
         cam = [None, None, None]
-        if ctx.camera_grads is not None:
-            for k, g in enumerate(ctx.camera_grads):
+        if camera_grads is not None:
+            for k, g in enumerate(camera_grads):
                 shape, device = ctx.camera_meta[k]
                 if g is not None and ctx.needs_input_grad[8 + k]:
                     cam[k] = g.reshape(shape).to(device)
-        return tuple(grads) + tuple(cam) + (None, None)
+        return grads + tuple(cam) + (None, None)
 
 
 def _deferring_owner(ctx):

@@ -528,3 +528,83 @@ def test_refused_combinations(device, mode):
     finally:
         for p in params:
             unregister_gradient_sink(p)
+
+
+# ------------------------------------------------------------------------------------------
+# 5. camera gradients behind an owner that claims gradient buffers
+# ------------------------------------------------------------------------------------------
+def _run_with_claiming_owner(sc, device, ws, bufs, accumulate):
+    """_hip with an owner registered on the inputs named in `bufs` that hands out (bufs[k], accumulate)."""
+    from diff_gaussian_rasterization import register_gradient_sink, unregister_gradient_sink
+
+    s, cams = _settings(sc, device)
+    t = _fresh(sc["leaves"])
+
+    class Owner:
+        def claim(self, p):
+            for k in bufs:
+                if p is t[k]:
+                    return bufs[k], accumulate
+            return None
+
+    owner = Owner()
+    for k in bufs:
+        register_gradient_sink(t[k], owner)
+    try:
+        outs, _ = _call(s, t, sc["aux"], camera_grads=True)
+        sum((w * o).sum() for w, o in zip(ws, outs)).backward()
+        torch.cuda.synchronize()
+    finally:
+        for k in bufs:
+            unregister_gradient_sink(t[k])
+    return t, cams
+
+
+def _garbage(sc, device):
+    g = torch.Generator(device="cpu").manual_seed(3)
+    return {k: torch.randn(sc["leaves"][k].shape, generator=g).to(device) for k in ("means3D", "opacities")}
+
+
+def test_overwriting_sink_with_camera_grads(device, mode):
+    """An owner that hands out (buffer, False) for means3D and opacities: the buffers hold the un-sunk
+    run's gradients bit for bit, the sunk inputs get no .grad, and every other Gaussian gradient and
+    the three camera gradients (fixed-order fp64 sums) are those of the un-sunk run."""
+    sc = _scene("small3", device)
+    ws = _weights(sc, device)
+    _, _, t0, c0 = _hip(sc, device, ws)
+    assert float(t0["means3D"].grad.abs().max()) > 0 and float(t0["opacities"].grad.abs().max()) > 0
+    bufs = _garbage(sc, device)
+    t, cams = _run_with_claiming_owner(sc, device, ws, bufs, False)
+    assert t["means3D"].grad is None and t["opacities"].grad is None  # sunk
+    for k in bufs:
+        assert torch.equal(bufs[k], t0[k].grad), k
+    for k in ("shs", "scales", "rotations", "means2D"):
+        assert torch.equal(t[k].grad, t0[k].grad), k
+    for a, b, nm in zip(cams, c0, NAMES):
+        assert a.grad is not None and float(a.grad.abs().max()) > 0 and torch.equal(a.grad, b.grad), nm
+
+
+def test_accumulating_sink_with_camera_grads(device, mode):
+    """An owner that hands out (buffer, True): the buffer ends as before + grad.  opacity: one fp32
+    old + new, exact (tests/test_gpu_aux.py::test_accumulating_sink).  means3D: that test's bound,
+    4 * 2^-24 (max|before| + max|grad|); without the aux outputs there is no depth-chain term, the sum
+    is one fp32 addition as well, and the exact comparison holds too."""
+    sc = _scene("small3", device)
+    ws = _weights(sc, device)
+    _, _, t0, c0 = _hip(sc, device, ws)
+    assert float(t0["means3D"].grad.abs().max()) > 0
+    before = _garbage(sc, device)
+    bufs = {k: v.clone() for k, v in before.items()}
+    t, cams = _run_with_claiming_owner(sc, device, ws, bufs, True)
+    assert t["means3D"].grad is None and t["opacities"].grad is None  # sunk
+    assert torch.equal(bufs["opacities"], before["opacities"] + t0["opacities"].grad)
+    want = before["means3D"] + t0["means3D"].grad
+    tol = 4 * 2.0 ** -24 * float(before["means3D"].abs().max() + t0["means3D"].grad.abs().max())
+    err = float((bufs["means3D"] - want).abs().max())
+    print(f"\n  means3D: max|buffer - (before + grad)| {err:.3e}  (bound {tol:.3e})")
+    assert err <= tol
+    assert torch.equal(bufs["means3D"], want)
+    for k in ("shs", "scales", "rotations", "means2D"):
+        assert torch.equal(t[k].grad, t0[k].grad), k
+    for a, b, nm in zip(cams, c0, NAMES):
+        assert torch.equal(a.grad, b.grad), nm

@@ -7,7 +7,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "gaussian-splatting-skysphere_amd"), ROOT]
+# GS_PKG: another copy of the package (an A/B of host-side changes in one call)
+sys.path[:0] = [os.environ.get("GS_PKG", os.path.join(ROOT, "gaussian-splatting-skysphere_amd")), ROOT]
 
 import torch  # noqa: E402
 
@@ -41,7 +42,7 @@ def fwd(counted):
 def bwd(out):
     nr, color, radii, geom, binning, img = out
     return X.backward(s.bg, sc.means3D, radii, e, sc.scales, sc.rotations, 1.0, e, s.viewmatrix, s.projmatrix,
-                      s.tanfovx, s.tanfovy, dpix, sc.shs, deg, s.campos, geom, nr, binning, img, False, None)
+                      s.tanfovx, s.tanfovy, dpix, sc.shs, deg, s.campos, geom, nr, binning, img, False, None, {}, 0)
 
 
 def timed(fn, idle, n):
