@@ -1203,13 +1203,26 @@ int gs_backward_render(int P, int D, int M, const float* background, int W, int 
                        const void* geom_buffer, long long num_rendered, const void* binning_buffer,
                        const void* image_buffer, const float* dL_dout_color, void* grad_buffer, float* dL_dmeans2D,
                        unsigned accumulate, int debug, void* stream) {
+  return gs_backward_render_aux(P, D, M, background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, nullptr,
+                                nullptr, grad_buffer, dL_dmeans2D, nullptr, accumulate, debug, stream);
+}
+
+int gs_backward_render_aux(int P, int D, int M, const float* background, int W, int H, const float* viewmatrix,
+                           const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                           const void* geom_buffer, long long num_rendered, const void* binning_buffer,
+                           const void* image_buffer, const float* dL_dout_color, const float* dL_dout_invdepth,
+                           const float* dL_dout_alpha, void* grad_buffer, float* dL_dmeans2D, float* invdepth_sums,
+                           unsigned accumulate, int debug, void* stream) {
   const CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
   clear_error(debug);
   if (P < 0) return set_error("P must be >= 0"), 1;
   if (W <= 0 || H <= 0) return set_error("image size must be positive (got %d x %d)", W, H), 1;
   if (P == 0) return 0;
   if (!viewmatrix || !projmatrix || !background) return set_error("missing required input pointer"), 1;
-  if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dout_color || !grad_buffer)
+  const bool with_aux = dL_dout_invdepth || dL_dout_alpha;
+  if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dout_color || !grad_buffer ||
+      (with_aux && !invdepth_sums))
     return set_error("missing buffer pointer"), 1;
   if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
   if (accumulate & ~GS_ACC_MEANS2D) return set_error("accumulate: only GS_ACC_MEANS2D applies here"), 1;
@@ -1219,8 +1232,20 @@ int gs_backward_render(int P, int D, int M, const float* background, int W, int 
   const GaussianArgs g = make_scene(P, D, M, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, nullptr,
                                     nullptr);
   float* gradrec = (float*)grad_buffer;
-  if (num_rendered > 0) bwd_render(P, c, L.geo, L.bin, L.img, dL_dout_color, gradrec, st);
-  bwd_records(g, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, dL_dmeans2D, accumulate, st);
+  // an aux gradient: the instances' side array behind the records (gs_grad_buffer_bytes_aux; its
+  // per-Gaussian tail is unused), the per-Gaussian sums in the caller's array; none: the plain path
+  BwdAux aux;
+  if (with_aux) {
+    size_t o_rec = 0;
+    grad_layout_aux((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)P, &o_rec, nullptr);
+    aux.d_invdepth = dL_dout_invdepth;
+    aux.d_alpha = dL_dout_alpha;
+    aux.gradrec_aux = (float*)((char*)grad_buffer + o_rec);
+    aux.gsum_aux = invdepth_sums;
+  }
+  if (num_rendered > 0) bwd_render(P, c, L.geo, L.bin, L.img, dL_dout_color, gradrec, st, aux);
+  bwd_records(g, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, dL_dmeans2D, accumulate, st,
+              aux);
   if (!t_failed && check_order_flags(false)) return 1;
   return t_failed ? 1 : 0;
 }
@@ -1328,6 +1353,21 @@ int gs_backward_gaussians_adam_stats(int P, int D, int M, const float* means3D, 
                                      double beta2, double eps, int maximize, const int* radii, const float* grad2d,
                                      int grad_stride, float* max_radii2D, float* grad_accum, float* denom, int debug,
                                      void* stream) {
+  return gs_backward_gaussians_adam_stats_aux(P, D, M, means3D, shs_dc, shs_rest, scales, scale_modifier, rotations,
+                                              view, params_host, exp_avg_host, exp_avg_sq_host, lr_host, step_host,
+                                              weight_decay_host, beta1, beta2, eps, maximize, radii, grad2d,
+                                              grad_stride, max_radii2D, grad_accum, denom, nullptr, debug, stream);
+}
+
+int gs_backward_gaussians_adam_stats_aux(int P, int D, int M, const float* means3D, const float* shs_dc,
+                                         const float* shs_rest, const float* scales, float scale_modifier,
+                                         const float* rotations, const gs_view_grad* view,
+                                         float* const* params_host, float* const* exp_avg_host,
+                                         float* const* exp_avg_sq_host, const double* lr_host,
+                                         const long long* step_host, const double* weight_decay_host, double beta1,
+                                         double beta2, double eps, int maximize, const int* radii,
+                                         const float* grad2d, int grad_stride, float* max_radii2D, float* grad_accum,
+                                         float* denom, const float* invdepth_sums, int debug, void* stream) {
   clear_error(debug);
   if (P < 0) return set_error("P must be >= 0"), 1;
   if (P == 0) return 0;
@@ -1367,6 +1407,8 @@ int gs_backward_gaussians_adam_stats(int P, int D, int M, const float* means3D, 
   GeomPtrs geo;
   geom_layout((size_t)P, &geo, (char*)view->geom_buffer);
   a.err = &geo.counters[CNT_ERR];
+  a.splat = geo.splat;  // (z of the depth chain)
+  a.invdepth_sums = invdepth_sums;
   const CameraArgs c = make_camera(nullptr, view->image_width, view->image_height, view->viewmatrix, view->projmatrix,
                                    view->campos, view->tan_fovx, view->tan_fovy, 0);
   bwd_gaussians_adam(g, c, geo, a, (hipStream_t)stream);

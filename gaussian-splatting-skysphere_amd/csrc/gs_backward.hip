@@ -559,6 +559,16 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
 // mean (row-vector convention of xf43: z = m . (view[2], view[6], view[10]) + view[14]), so
 // dL/dz = -s9 / z^2 and dL/dmeans3D[i] += dL/dz (view[2], view[6], view[10]): an fp32 old + new after
 // the kernel that wrote the row.  Gaussians without instances have no sum (and no term).
+// depth_chain_add: the term's arithmetic, shared with the fused backward + Adam (k_preprocess_bwd_adam<*, true>
+// adds it to the row value in registers), so both produce the same floats.
+__device__ __forceinline__ void depth_chain_add(float& dx, float& dy, float& dz3, float s9, float z,
+                                                const float* __restrict__ view) {
+  const float dz = -s9 / (z * z);
+  dx = dx + dz * view[2];
+  dy = dy + dz * view[6];
+  dz3 = dz3 + dz * view[10];
+}
+
 __global__ __launch_bounds__(256) void k_depth_chain_aux(int P, const uint32_t* __restrict__ tiles,
                                                          const float4* __restrict__ splat,
                                                          const float* __restrict__ gsum_aux,
@@ -566,11 +576,8 @@ __global__ __launch_bounds__(256) void k_depth_chain_aux(int P, const uint32_t* 
                                                          float* __restrict__ dmean3D) {
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   if (i >= P || tiles[i] == 0) return;
-  const float z = splat[3 * i + 2].y;
-  const float dz = -gsum_aux[i] / (z * z);
-  dmean3D[3 * i + 0] = dmean3D[3 * i + 0] + dz * view[2];
-  dmean3D[3 * i + 1] = dmean3D[3 * i + 1] + dz * view[6];
-  dmean3D[3 * i + 2] = dmean3D[3 * i + 2] + dz * view[10];
+  float* d = dmean3D + 3 * (size_t)i;
+  depth_chain_add(d[0], d[1], d[2], gsum_aux[i], splat[3 * i + 2].y, view);
 }
 
 void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BwdAux& aux,
@@ -1157,7 +1164,10 @@ __device__ __forceinline__ void adam_sh_block(const FusedAdamArgs& a, int tk, in
   }
 }
 
-template <int DEG>
+// AUX (gs_backward_gaussians_adam_stats_aux): the aux backward's depth chain is added to the finished
+// dL/dmeans3D in registers, k_depth_chain_aux's floats (depth_chain_add); the plain instantiations
+// are the kernels they were.
+template <int DEG, bool AUX = false>
 __global__ __launch_bounds__(256) void k_preprocess_bwd_adam(GaussianArgs g, CameraArgs c,
                                                              const uint32_t* __restrict__ tiles,
                                                              const uint8_t* __restrict__ clamped,
@@ -1204,7 +1214,8 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_adam(GaussianArgs g, Cam
     }
     RegSink gr;
     gr.dop = 0.0f;
-    if (tiles[i] == 0) {  // invisible: every gradient is zero (the Adam step still runs on them)
+    const bool visible = tiles[i] != 0;
+    if (!visible) {  // invisible: every gradient is zero (the Adam step still runs on them)
 #pragma unroll
       for (int k = 0; k < KF; k++) row[k] = 0.0f;
     } else {
@@ -1219,6 +1230,11 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_adam(GaussianArgs g, Cam
     const float gq_in[4] = {gr.dr[0], gr.dr[1], gr.dr[2], gr.dr[3]}, q[4] = {pq.x, pq.y, pq.z, pq.w};
     float gq[4];
     normalize_adjoint(gq_in, q, gq);
+    // (here, past the SH rows' registers: added before them it cost the degree-3 kernel a wave per SIMD)
+    if constexpr (AUX)
+      if (visible)
+        depth_chain_add(gr.dmean[0], gr.dmean[1], gr.dmean[2], a.invdepth_sums[i], a.splat[3 * (size_t)i + 2].y,
+                        c.view);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       adam_update(px[k], gr.dmean[k], mx[k], vx[k], a.k, a.nss[DT_XYZ], a.bc2s[DT_XYZ], a.wd[DT_XYZ]);
@@ -1263,8 +1279,15 @@ void bwd_gaussians_adam(const GaussianArgs& g, const CameraArgs& c, const GeomPt
                         hipStream_t st) {
   if (g.P <= 0) return;
   const dim3 grid((g.P + 255) / 256), block(256);
-#define GS_PBWD_ADAM(D) \
-  GS_LAUNCH("preprocess_bwd_adam", k_preprocess_bwd_adam<D>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, a)
+#define GS_PBWD_ADAM(D)                                                                                          \
+  do {                                                                                                          \
+    if (a.invdepth_sums)                                                                                        \
+      GS_LAUNCH("preprocess_bwd_adam_aux", (k_preprocess_bwd_adam<D, true>), grid, block, 0, st, g, c, geo.tiles, \
+                geo.clamped, geo.gsum, a);                                                                      \
+    else                                                                                                        \
+      GS_LAUNCH("preprocess_bwd_adam", (k_preprocess_bwd_adam<D, false>), grid, block, 0, st, g, c, geo.tiles,  \
+                geo.clamped, geo.gsum, a);                                                                      \
+  } while (0)
   switch (g.D) {
     case 0: GS_PBWD_ADAM(0); break;
     case 1: GS_PBWD_ADAM(1); break;
@@ -1525,9 +1548,9 @@ __global__ __launch_bounds__(256) void k_mean2d_grad(int P, const uint32_t* __re
 }
 
 void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img, float* gradrec,
-                 uint32_t R, bool have_records, float* dmean2D, uint32_t acc, hipStream_t st) {
+                 uint32_t R, bool have_records, float* dmean2D, uint32_t acc, hipStream_t st, const BwdAux& aux) {
   if (g.P <= 0) return;
-  if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st);
+  if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st, aux);
   if (dmean2D)
     GS_LAUNCH("mean2d_grad", k_mean2d_grad, dim3((g.P + 255) / 256), dim3(256), 0, st, g.P, geo.tiles, geo.gsum,
               dmean2D, acc);

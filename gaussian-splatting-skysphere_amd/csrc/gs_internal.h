@@ -528,7 +528,8 @@ void fwd_preprocess_views(const GaussianArgs& g, const PreViews& pv, hipStream_t
 // the per-tile half of a split backward: record sums into the geom buffer (+ dL/dmeans2D)
 // R: the binning buffer's instance count / capacity (gradrec holds R records + the record-sum scratch)
 void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img, float* gradrec,
-                 uint32_t R, bool have_records, float* dmean2D, uint32_t acc, hipStream_t st);
+                 uint32_t R, bool have_records, float* dmean2D, uint32_t acc, hipStream_t st,
+                 const BwdAux& aux = BwdAux());
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
                     bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux = BwdAux());
@@ -638,6 +639,10 @@ struct FusedAdamArgs {
   const float* grad2d;
   int gstride;
   float *max_r, *accum, *denom;
+  // the aux backward's depth chain (gs_backward_gaussians_adam_stats_aux; invdepth_sums == nullptr:
+  // none, the plain instantiations): the view's splat records (z) and its per-Gaussian dL/d(1 / z) sums
+  const float4* splat;
+  const float* invdepth_sums;
 };
 // one view's per-Gaussian half fused with the Adam step (g: M == 16 split SH rows, 16-B aligned)
 void bwd_gaussians_adam(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const FusedAdamArgs& a,

@@ -530,9 +530,19 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
 
 
 def backward_render(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, dL_dout_color, P, degree, M,
-                    geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug):
+                    geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug, aux_grads=None):
     """Per-tile half of the backward (gs_backward_render): the view's per-Gaussian record sums,
-    kept in geomBuffer for backward_gaussians, and its dL_dmeans2D [P, 3] (or None)."""
+    kept in geomBuffer for backward_gaussians, and its dL_dmeans2D [P, 3] (or None).
+    aux_grads: (dL_dout_invdepth, dL_dout_alpha) of a rasterize_gaussians_aux forward, either may be
+    None (gs_backward_render_aux, over ctypes); the return is then (dL_dmeans2D, invdepth_sums): the
+    [P] per-Gaussian dL/d(1 / z) sums of the depth chain (written for Gaussians with instances only),
+    the input of FusedAdam.prepare_fused_backward."""
+    if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
+        aux_grads = None
+    if aux_grads is not None:
+        return _backward_render_aux(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, dL_dout_color,
+                                    P, degree, M, geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug,
+                                    aux_grads)
     if _EXT is not None and geomBuffer.is_cuda:
         return _EXT.backward_render(background, viewmatrix, projmatrix, campos, float(tan_fovx), float(tan_fovy),
                                     dL_dout_color, int(P), int(degree), int(M), geomBuffer, int(R), binningBuffer,
@@ -555,6 +565,33 @@ def backward_render(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fo
                                     int(bool(debug)), st),
             "rasterize_gaussians_backward (render half)")
     return dm2
+
+
+def _backward_render_aux(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, dL_dout_color, P, degree, M,
+                         geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug, aux_grads):
+    dev = geomBuffer.device
+    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    dm2 = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_means2D else None
+    sums = torch.empty((P,), dtype=torch.float32, device=dev)
+    if P == 0:
+        return dm2, sums
+    bg, view, proj, cam = _camera_side(dev, background, viewmatrix, projmatrix, campos)
+    dpix = _f32(dL_dout_color, "dL_dout_color", dev)
+    d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
+    for t in (d_inv, d_alpha):
+        if t is not None and t.numel() != H * W:
+            raise RuntimeError("aux gradients must have shape (1, H, W)")
+    R = binning_layout_count(R, binningBuffer, W, H)
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes_aux(R, P),), dtype=torch.uint8, device=dev)
+        _native.check(
+            _lib.gs_backward_render_aux(P, int(degree), int(M), _ptr(bg), W, H, _ptr(view), _ptr(proj), _ptr(cam),
+                                        float(tan_fovx), float(tan_fovy), _ptr(geomBuffer), int(R),
+                                        _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix), _ptr(d_inv), _ptr(d_alpha),
+                                        _ptr(grad_scratch), _ptr(dm2), _ptr(sums), 0, int(bool(debug)), st),
+            "rasterize_gaussians_backward (render half, aux outputs)")
+    return dm2, sums
 
 
 def backward_gaussians(means3D, sh, colors, scales, rotations, cov3D_precomp, scale_modifier, degree, views, outs,

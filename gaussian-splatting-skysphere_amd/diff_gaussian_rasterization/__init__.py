@@ -68,9 +68,16 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
 #       (_C.backward_render, dL/dmeans2D returned to autograd), nothing is claimed, and defer_view
 #       gets inputs = dict(means3D, sh, colors, scales, rotations, cov3D, scale_modifier, degree,
 #       debug, sh_rest) and view = (viewmatrix, projmatrix, campos, tanfovx, tanfovy, W, H,
-#       geomBuffer) for _C.backward_gaussians.  Aux gradients and camera gradients refuse such an owner.
+#       geomBuffer) for _C.backward_gaussians.  Camera gradients refuse such an owner, and so do aux
+#       gradients unless it opts in (accepts_aux).
 #   owner.accepts_sh_split (a true attribute)   a deferring owner that handles split SH rows
 #       (inputs["sh_rest"]); without it a deferred sh_split view is refused.
+#   owner.accepts_aux (a true attribute)   a deferring owner that takes a backward with an alpha /
+#       inverse-depth gradient (gs_train_step._AdamBackward; GradBucket does not): the aux per-tile half
+#       runs (_C.backward_render(aux_grads=...)) and such an owner's defer_view inputs carry one more key,
+#       inputs["invdepth_sums"]: the [P] fp32 per-Gaussian dL/d(1 / z) sums whose depth-chain term the
+#       owner's per-Gaussian half must add to dL/dmeans3D (gs_backward_gaussians_adam_stats_aux), or
+#       None for a plain backward.  The alpha gradient needs nothing per Gaussian.
 # What an owner may read from the `ctx` it is handed: ctx.sinks, the call's registered inputs that
 # require grad as [(input index, gradient name, tensor, owner)] in _SINK_INPUTS order, and
 # ctx.needs_input_grad[0:8], the same eight inputs in every Function.  Nothing else of ctx is stable.
@@ -325,8 +332,9 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
     either may be None; camera: None, or whether dL/dcampos is wanted.  -> (the eight Gaussian
     gradients in input order, None where an owner's buffer or a deferred pass received it; the
     camera gradients (dL/dviewmatrix, dL/dprojmatrix, dL/dcampos or None), or None without `camera`
-    or when no output reached the loss).  A deferring owner takes the view here; the callers that
-    cannot be deferred (aux gradients, camera gradients) refuse it first."""
+    or when no output reached the loss).  A deferring owner takes the view here (with aux gradients
+    only one that has `accepts_aux`); the callers that cannot be deferred (aux gradients to another
+    owner, camera gradients) refuse it first."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None  # only the colour reached the loss (or nothing did): the plain backward
     if grad_out_color is None and aux_grads is None:  # no output reached the loss
@@ -355,10 +363,15 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
         dm2 = _C.backward_render(s.bg, view, proj, s.campos, s.tanfovx, s.tanfovy, grad_out_color.contiguous(),
                                  means3D.size(0), s.sh_degree, M,
                                  geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, ctx.needs_input_grad[1],
-                                 s.debug)
+                                 s.debug, **({} if aux_grads is None else {"aux_grads": aux_grads}))
+        more = {}
+        if getattr(deferrer, "accepts_aux", False):  # (the other owners' inputs are what they were)
+            more["invdepth_sums"] = None
+            if aux_grads is not None:
+                dm2, more["invdepth_sums"] = dm2
         deferrer.defer_view(ctx, dict(means3D=means3D, sh=sh, colors=colors_precomp, scales=scales,
                                       rotations=rotations, cov3D=cov3Ds_precomp, scale_modifier=s.scale_modifier,
-                                      degree=s.sh_degree, debug=s.debug, sh_rest=ctx.sh_rest),
+                                      degree=s.sh_degree, debug=s.debug, sh_rest=ctx.sh_rest, **more),
                             (view, proj, s.campos, s.tanfovx, s.tanfovy, s.image_width, s.image_height,
                              geomBuffer))
         return (None, dm2) + (None,) * 6, None
@@ -420,7 +433,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 # inverse depth one of colour 1 / z_i (its gradient also reaches means3D through z_i).  Colour and
 # radii are bit-identical to the plain call's, and a backward that receives no aux gradient runs
 # the plain backward.  Aux calls take the two-call path over ctypes (not _gs_ext); prepared views,
-# bounded forwards and deferring gradient owners are refused.
+# bounded forwards and deferring gradient owners that do not opt in (owner.accepts_aux) are refused.
 # ------------------------------------------------------------------------------------------
 def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                             raster_settings, sh_split=None):
@@ -439,7 +452,10 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_invdepth, grad_alpha):
         # without an aux gradient the backward is the plain one, which a deferring owner may take
-        if (grad_invdepth is not None or grad_alpha is not None) and _deferring_owner(ctx) is not None:
+        # (so may one with an aux gradient, by an owner that opted in: accepts_aux)
+        deferrer = _deferring_owner(ctx)
+        if ((grad_invdepth is not None or grad_alpha is not None) and deferrer is not None
+                and not getattr(deferrer, "accepts_aux", False)):
             raise RuntimeError("aux_outputs: an alpha / inverse-depth gradient is not supported with a deferring "
                                "gradient owner (GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
         return _backward_step(ctx, grad_out_color, (grad_invdepth, grad_alpha))[0] + (None, None)

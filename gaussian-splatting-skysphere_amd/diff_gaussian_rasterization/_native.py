@@ -154,6 +154,18 @@ SIGNATURES = {
          _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
          _c_p, ctypes.c_uint, _c_p, _c_i, _c_p],
     ),
+    # GSRAST_HAS_AUX_DEFERRED: the per-tile half with the aux gradients, and the fused per-Gaussian
+    # half + Adam with the inverse depth's chain
+    "gs_backward_render_aux": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_p, _c_p, _c_p, ctypes.c_uint, _c_i, _c_p],
+    ),
+    "gs_backward_gaussians_adam_stats_aux": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, ctypes.POINTER(ViewGrad), _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_p, _c_d, _c_d, _c_d, _c_i, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p],
+    ),
     # GSRAST_HAS_CAMERA_GRAD: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos of one view after its backward
     "gs_camera_grad_scratch_bytes": (_c_sz, [_c_i]),
     "gs_backward_camera": (

@@ -230,6 +230,9 @@ class FusedAdam(torch.optim.Optimizer):
         stats: (max_radii2D, xyz_gradient_accum, denom, radii, viewspace_grad) -- the view's
         densification statistics (densify_stats, train.py:115-116) in the same pass
         (gs_backward_gaussians_adam_stats), the same floats as densify_stats after the step.
+        inputs["invdepth_sums"] (a [P] tensor, the aux per-tile half's output; absent or None: a plain
+        backward): the inverse depth's chain into dL/dmeans3D is applied before the update
+        (gs_backward_gaussians_adam_stats_aux), the same floats as the unfused aux backward.
         Returns the launch: every check and argument is done here, so a caller that must read the
         loss first (train.py:99 before :127) prepares before that host sync and launches after it;
         the step counts advance at the launch."""
@@ -283,14 +286,22 @@ class FusedAdam(torch.optim.Optimizer):
             stat_args = [_ptr(radii), _ptr(vgrad), vgrad.shape[1], _ptr(max_r), _ptr(accum), _ptr(denom)]
         else:
             stat_args = [None, None, 0, None, None, None]
+        sums = inputs.get("invdepth_sums")
+        if sums is not None:
+            _check_f32_dense(sums, "FusedAdam invdepth_sums")
+            if tuple(sums.shape) != (P,) or sums.device != dev:
+                raise ValueError(f"step_fused_backward: invdepth_sums of shape {tuple(sums.shape)} on {sums.device}, "
+                                 f"expected ({P},) on {dev}")
         arr = lambda ts: ctypes.cast((ctypes.c_void_p * 6)(*[t.data_ptr() for t in ts]), ctypes.c_void_p)  # noqa: E731
         steps_c = (ctypes.c_longlong * 6)()
         args = [P, int(inputs["degree"]), 16, _ptr(xyz), _ptr(dc), _ptr(rest), _ptr(scales),
                 float(inputs["scale_modifier"]), _ptr(rots), ctypes.byref(vg), arr(params), arr(ms), arr(vs),
                 ctypes.cast((ctypes.c_double * 6)(*lrs), ctypes.c_void_p), ctypes.cast(steps_c, ctypes.c_void_p),
                 ctypes.cast((ctypes.c_double * 6)(*wds), ctypes.c_void_p), b1, b2, eps, int(maximize), *stat_args,
-                int(bool(inputs.get("debug", False))), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)]
-        keep = (vm, pm, cp, geom, vg, inputs, stats)  # alive until the launch
+                *([] if sums is None else [_ptr(sums)]), int(bool(inputs.get("debug", False))),
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)]
+        keep = (vm, pm, cp, geom, vg, inputs, stats, sums)  # alive until the launch
+        entry = _lib.gs_backward_gaussians_adam_stats if sums is None else _lib.gs_backward_gaussians_adam_stats_aux
 
         def launch(defer_commit: bool = False):
             """Advances the step counts and launches.  defer_commit: launches with the next step
@@ -301,7 +312,7 @@ class FusedAdam(torch.optim.Optimizer):
             for k, p in enumerate(params):
                 steps_c[k] = self._peek_step(p) if defer_commit else self._advance(p)[2]
             with torch.cuda.device(dev):
-                _native.check(_lib.gs_backward_gaussians_adam_stats(*args), "backward + adam step (fused)")
+                _native.check(entry(*args), "backward + adam step (fused)")
             assert keep  # (the closure holds the arguments' tensors until the launch)
             if defer_commit:
                 def commit():

@@ -24,10 +24,12 @@ densification statistics, percent_dense and active_sh_degree.  The learning-rate
 from __future__ import annotations
 
 import threading
+import weakref
 
 import torch
 
 import gs_loss
+import gs_sky
 import gs_train
 from diff_gaussian_rasterization import GaussianRasterizer, _C, bounded_status, register_gradient_sink, \
     unregister_gradient_sink
@@ -78,10 +80,21 @@ class TrainModel:
         self.max_radii2D = torch.zeros((P,), device=device)
         self.xyz_gradient_accum = torch.zeros((P, 1), device=device)
         self.denom = torch.zeros((P, 1), device=device)
+        self.sky = self.sky_optimizer = None  # attach_sky
 
     @property
     def P(self) -> int:
         return self._xyz.shape[0]
+
+    def attach_sky(self, sky, lr: float = FEATURE_LR):
+        """A learnable sky behind the splats (a gs_sky.SkySphere on the model's device), trained by
+        train_step(sky=True).  Its texture gets an optimizer of its own (one group "sky", the class of
+        self.optimizer, eps 1e-15): densify_and_prune's optimizer surgery walks every group of
+        self.optimizer by Gaussian row, and the texture has none."""
+        self.sky = sky
+        self.sky_optimizer = type(self.optimizer)([{"params": [sky.texture], "lr": lr, "name": "sky"}], lr=0.0,
+                                                  eps=1e-15)
+        return sky
 
     # the reference getters in torch (gaussian_model.py:95-115), for fused=False
     def torch_render_inputs(self):
@@ -99,6 +112,7 @@ class _AdamBackward:
 
     defers = True
     accepts_sh_split = True
+    accepts_aux = True  # a sky's alpha gradient, a depth prior's inverse-depth gradient (inputs["invdepth_sums"])
 
     def __init__(self):
         self.tensors, self.pending, self.geom = [], None, None
@@ -130,7 +144,7 @@ class _AdamBackward:
 
 
 def render(model: TrainModel, settings, fused: bool = True, act_leaves: list | None = None, split_sh: bool = True,
-           binning_capacity: int | None = None, sink_owner=None, row_waits=None):
+           binning_capacity: int | None = None, sink_owner=None, row_waits=None, aux_outputs: bool = False):
     """gaussian_renderer.render() for the default pipe (SH and covariance in the rasterizer).
     act_leaves (a list): the activated inputs are made autograd leaves (their adjoint then runs in
     FusedAdam.step_activated) and appended to it as (shs, opacity, scales, rotations).
@@ -138,7 +152,8 @@ def render(model: TrainModel, settings, fused: bool = True, act_leaves: list | N
     sink_owner: armed on xyz and the activated leaves before the rasterizer call (_AdamBackward).
     row_waits (fused=True, the autograd activation; [(lo, hi, event)] from row 0): the parameters'
     rows become ready chunk by chunk on other streams (ShardedAdam's all-gathers of the previous
-    step); the activation and the rasterizer's preprocess run chunk by chunk behind them."""
+    step); the activation and the rasterizer's preprocess run chunk by chunk behind them.
+    aux_outputs: the rasterizer's aux call; returns (image, screenspace_points, radii, invdepth, alpha)."""
     if row_waits and (act_leaves is not None or not fused):
         raise ValueError("render: row_waits apply to the fused autograd activation only")
     sh_split = None
@@ -174,13 +189,13 @@ def render(model: TrainModel, settings, fused: bool = True, act_leaves: list | N
     # leaf; the rasterizer never reads its values (only its .grad is written), so no fill launch
     screenspace_points = torch.empty_like(means3D, requires_grad=True)
     with _C.row_waits(act_waits):
-        image, radii = GaussianRasterizer(raster_settings=settings)(
+        out = GaussianRasterizer(raster_settings=settings)(
             means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=opacity,
             scales=scales, rotations=rotations, cov3D_precomp=None, sh_split=sh_split,
-            binning_capacity=binning_capacity)
+            binning_capacity=binning_capacity, **({"aux_outputs": True} if aux_outputs else {}))
     if act_waits:  # (the preprocess waited for every chunk; anything after it on this stream sees all rows)
         torch.cuda.current_stream(means3D.device).wait_event(act_waits[-1][2])
-    return image, screenspace_points, radii
+    return (out[0], screenspace_points) + tuple(out[1:])
 
 
 def _torch_densification_stats(model: TrainModel, viewspace, radii):
@@ -206,9 +221,23 @@ def _pinned_words(device):
     return b
 
 
+_BG_ZERO: dict = {}  # id(bg tensor) -> (weakref, _version, all zeros?)
+
+
+def _bg_is_zero(bg: torch.Tensor) -> bool:
+    """(bg == 0).all(), memoised per tensor and version: one host read-back per settings, not per step."""
+    e = _BG_ZERO.get(id(bg))
+    if e is None or e[0]() is not bg or e[1] != bg._version:
+        if len(_BG_ZERO) > 256:
+            _BG_ZERO.clear()
+        e = _BG_ZERO[id(bg)] = (weakref.ref(bg), bg._version, not bool((bg != 0).any()))
+    return e[2]
+
+
 def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool = True, densify_stats: bool = True,
                lambda_dssim: float = LAMBDA_DSSIM, fused_adjoint: bool = True, split_sh: bool = True,
-               loss_item: bool = False, binning_capacity: int | None = None, fuse_adam: bool = False):
+               loss_item: bool = False, binning_capacity: int | None = None, fuse_adam: bool = False,
+               sky=None, depth_prior: torch.Tensor | None = None, depth_weight: float = 0.0):
     """One iteration (module docstring).  Returns the loss tensor, or with loss_item=True the
     reference's per-iteration `loss.item()` (train.py:99, its progress-bar EMA): a host read-back
     that waits for the forward and backward, taken where train.py takes it (before the statistics
@@ -226,18 +255,56 @@ def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool 
     the backward runs fused with the Adam step, in one pass over the Gaussians where train.py runs
     optimizer.step() (_AdamBackward, FusedAdam.step_fused_backward): no gradient of the six
     parameters is ever stored; parameters and moments bit-identical to the unfused step, the
-    screen-space carrier's .grad (the densification statistics' input) as there."""
+    screen-space carrier's .grad (the densification statistics' input) as there.
+    sky (True: model.sky of TrainModel.attach_sky; or a gs_sky.SkySphere whose texture
+    model.sky_optimizer holds): the loss sees gs_sky.compose(color, alpha, sky.texture, settings), the
+    sky behind the splats (settings.bg must be all zeros), and the texture is stepped by
+    model.sky_optimizer where train.py steps the optimizer.
+    depth_prior ([1, H, W]) with depth_weight > 0: depth_weight * |invdepth - depth_prior|.mean() is
+    added to the loss (inverse-depth regularisation on the rasterizer's expected inverse depth).
+    Both run the rasterizer's aux call and work on every path above except binning_capacity (the aux
+    forward is not bounded): with fuse_adam the alpha / inverse-depth gradients go through the
+    deferred aux backward (_AdamBackward.accepts_aux), bit-identical to the unfused step.  An invalid
+    view raises with the texture, its moments and its step count untouched as well."""
+    with_depth = depth_prior is not None and depth_weight > 0
+    if sky is not None and sky is not False:
+        if sky is True:
+            sky = model.sky
+        if sky is None or model.sky_optimizer is None:
+            raise ValueError("train_step: sky= needs TrainModel.attach_sky first")
+        if not any(p is sky.texture for g in model.sky_optimizer.param_groups for p in g["params"]):
+            raise ValueError("train_step: sky= is not the sky of model.sky_optimizer (TrainModel.attach_sky)")
+    else:
+        sky = None
+    aux = sky is not None or with_depth
+    if aux and binning_capacity is not None:
+        raise ValueError("train_step: sky= / depth_prior= are not supported with a bounded forward "
+                         "(binning_capacity=)")
+    if sky is not None and not _bg_is_zero(settings.bg):
+        raise ValueError("render_with_sky: settings.bg must be all zeros (the sky is the background)")
+    if with_depth and tuple(depth_prior.shape) != (1, int(settings.image_height), int(settings.image_width)):
+        raise ValueError(f"train_step: depth_prior must be [1, {settings.image_height}, {settings.image_width}] "
+                         f"(got {tuple(depth_prior.shape)})")
+    sky_opt = model.sky_optimizer if sky is not None else None
     acts = [] if (fused and fused_adjoint) else None
     owner = None
     if fuse_adam and acts is not None and split_sh and model._features_rest.shape[1] == 15:
         owner = _AdamBackward()
     try:
-        image, viewspace, radii = render(model, settings, fused, acts, split_sh, binning_capacity, owner)
+        if aux:
+            image, viewspace, radii, invdepth, alpha = render(model, settings, fused, acts, split_sh, None, owner,
+                                                              aux_outputs=True)
+            if sky is not None:
+                image = gs_sky.compose(image, alpha, sky.texture, settings)
+        else:
+            image, viewspace, radii = render(model, settings, fused, acts, split_sh, binning_capacity, owner)
         if fused:  # the whole loss expression in one fused forward / backward (gs_loss.photometric_loss)
             loss, Ll1 = gs_loss.photometric_loss(image, gt_image, lambda_dssim)
         else:
             Ll1 = gs_loss.l1_loss(image, gt_image)
             loss = (1.0 - lambda_dssim) * Ll1 + lambda_dssim * (1.0 - gs_loss.ssim(image, gt_image))
+        if with_depth:
+            loss = loss + depth_weight * (invdepth - depth_prior).abs().mean()
         early = None
         if loss_item and owner is not None and owner.geom is not None:
             # fused Adam: the loss value and the view's forward error flags are copied out right after
@@ -288,6 +355,9 @@ def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool 
             if binning_capacity is not None:
                 bounded_status()  # earlier bounded forwards' flags (this view's update stands)
             with torch.no_grad():
+                if sky_opt is not None:
+                    sky_opt.step()
+                    sky_opt.zero_grad(set_to_none=True)
                 model.optimizer.zero_grad(set_to_none=True)
             return value
         if loss_item:
@@ -326,7 +396,16 @@ def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool 
                      model._rotation: ("normalize", rots.grad)}, sh_coeffs=shs.shape[1])
             else:
                 model.optimizer.step()
+            if sky_opt is not None:
+                sky_opt.step()
+                sky_opt.zero_grad(set_to_none=True)
             model.optimizer.zero_grad(set_to_none=True)
+    except BaseException:
+        # an invalid view (raised above, or by the rasterizer's backward behind the sky's): the texture's
+        # gradient must not reach the next iteration either
+        if sky_opt is not None:
+            sky_opt.zero_grad(set_to_none=True)
+        raise
     finally:
         if owner is not None:
             owner.disarm()

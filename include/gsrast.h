@@ -72,6 +72,11 @@ extern "C" {
 /* Camera gradients (additive, same ABI version): gs_camera_grad_scratch_bytes, gs_backward_camera. */
 #define GSRAST_HAS_CAMERA_GRAD 1
 
+/* Deferred aux backward (additive, same ABI version): gs_backward_render_aux (the per-tile half with
+ * the aux outputs' gradients), gs_backward_gaussians_adam_stats_aux (the fused per-Gaussian half +
+ * Adam with the inverse depth's chain into dL/dmeans3D). */
+#define GSRAST_HAS_AUX_DEFERRED 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -411,6 +416,20 @@ int gs_backward_render(int P, int D, int M, const float* background, int image_w
                        float tan_fovy, const void* geom_buffer, long long num_rendered, const void* binning_buffer,
                        const void* image_buffer, const float* dL_dout_color, void* grad_buffer, float* dL_dmeans2D,
                        unsigned accumulate, int debug, void* stream);
+/* gs_backward_render_aux (GSRAST_HAS_AUX_DEFERRED): gs_backward_render with the aux outputs'
+ *   gradients dL_dout_invdepth / dL_dout_alpha ([H, W] each, either may be NULL).  Both NULL: exactly
+ *   gs_backward_render's launches (invdepth_sums is not touched and may be NULL).  Otherwise
+ *   grad_buffer >= gs_grad_buffer_bytes_aux(num_rendered, P) and invdepth_sums [P] (required) receives
+ *   every visible Gaussian's sum of dL/d(1 / z_i) over its instances -- the input of the depth chain
+ *   that gs_backward_gaussians_adam_stats_aux adds to dL/dmeans3D; the alpha gradient needs nothing
+ *   per Gaussian (it is part of the record sums in geom_buffer).  With num_rendered == 0 nothing is
+ *   summed and invdepth_sums must not be read (as in gs_backward_accumulate_aux). */
+int gs_backward_render_aux(int P, int D, int M, const float* background, int image_width, int image_height,
+                           const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                           float tan_fovy, const void* geom_buffer, long long num_rendered,
+                           const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                           const float* dL_dout_invdepth, const float* dL_dout_alpha, void* grad_buffer,
+                           float* dL_dmeans2D, float* invdepth_sums, unsigned accumulate, int debug, void* stream);
 int gs_backward_gaussians(int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
                           const float* scales, float scale_modifier, const float* rotations,
                           const float* cov3D_precomp, int num_views, const gs_view_grad* views, float* dL_dcolors,
@@ -581,6 +600,22 @@ int gs_backward_gaussians_adam_stats(int P, int D, int M, const float* means3D, 
                                      double beta2, double eps, int maximize, const int* radii, const float* grad2d,
                                      int grad_stride, float* max_radii2D, float* grad_accum, float* denom, int debug,
                                      void* stream);
+
+/* gs_backward_gaussians_adam_stats_aux (GSRAST_HAS_AUX_DEFERRED): gs_backward_gaussians_adam_stats
+ * after a gs_backward_render_aux that was given an aux gradient.  invdepth_sums [P] is that call's
+ * output: every Gaussian with instances gets -invdepth_sums[i] / z_i^2 * (view[2], view[6], view[10])
+ * added to its dL/dmeans3D (z_i from the view's geometry buffer) before the Adam update -- the same
+ * floats as gs_backward_accumulate_aux's depth chain followed by gs_adam_step_activated.
+ * invdepth_sums NULL: exactly gs_backward_gaussians_adam_stats. */
+int gs_backward_gaussians_adam_stats_aux(int P, int D, int M, const float* means3D, const float* shs_dc,
+                                         const float* shs_rest, const float* scales, float scale_modifier,
+                                         const float* rotations, const gs_view_grad* view,
+                                         float* const* params_host, float* const* exp_avg_host,
+                                         float* const* exp_avg_sq_host, const double* lr_host,
+                                         const long long* step_host, const double* weight_decay_host, double beta1,
+                                         double beta2, double eps, int maximize, const int* radii,
+                                         const float* grad2d, int grad_stride, float* max_radii2D, float* grad_accum,
+                                         float* denom, const float* invdepth_sums, int debug, void* stream);
 
 /* ---- render() inputs from GaussianModel's raw parameters  <-  get_features / get_opacity /
  *      get_scaling / get_rotation (/root/reference/scene/gaussian_model.py:95-115, read at
