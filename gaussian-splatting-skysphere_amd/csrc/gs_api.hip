@@ -1439,6 +1439,8 @@ unsigned gs_debug_set_scan_spin_limit(unsigned limit) {
   return gs::g_spin_limit.exchange(limit, std::memory_order_relaxed);
 }
 
+int gs_debug_sh_rows_staged(int D, int M, const void* shs) { return gs::sh_rows_stageable(D, M, shs) ? 1 : 0; }
+
 /* ---- launched-kernel log (tests: every kernel in the code object is launched by some test) ---- */
 int gs_debug_launch_log(int enable) {
   const int prev = gs::launch_log_on();

@@ -26,14 +26,14 @@ namespace gs {
 // SH -> RGB for one Gaussian, channel-major evaluation order identical to oracle/gs_oracle.c
 // sh_eval_one (reference: /root/reference/utils/sh_utils.py:57-100, +0.5 and clamp_min(0) as
 // /root/reference/gaussian_renderer/__init__.py:77-78).
-// rest != null: split rows (sh = the Gaussian's features_dc row, rest = its features_rest row),
+// split: split rows (sh = the Gaussian's features_dc row, rest = its features_rest row),
 // read as 12-B pieces; the evaluation is the same.
+// The Gaussian's 3 (DEG + 1)^2 coefficients s[3 k + c] from its global row(s); split: a uniform flag.
 template <int DEG>
-__device__ __forceinline__ void sh_to_rgb(const float* __restrict__ sh, const float* __restrict__ rest, int M, float x,
-                                          float y, float z, float* rgb, uint32_t& clamped) {
+__device__ __forceinline__ void sh_row_load(const float* __restrict__ sh, const float* __restrict__ rest, bool split,
+                                            int M, float* s) {
   constexpr int K = (DEG + 1) * (DEG + 1);
-  float s[K * 3];
-  if (rest) {
+  if (split) {
     const F3 d = *reinterpret_cast<const F3*>(sh);
     s[0] = d.a, s[1] = d.b, s[2] = d.c;
     const F3* r3 = reinterpret_cast<const F3*>(rest);
@@ -56,6 +56,20 @@ __device__ __forceinline__ void sh_to_rgb(const float* __restrict__ sh, const fl
 #pragma unroll
     for (int k = 0; k < K * 3; k++) s[k] = sh[k];
   }
+}
+// The same coefficients from the Gaussian's staged LDS row (stage_sh_rows): whole 16-B reads.
+template <int DEG>
+__device__ __forceinline__ void sh_row_load_lds(const float* row, float* s) {
+  constexpr int KF = 3 * (DEG + 1) * (DEG + 1);
+  static_assert(KF % 4 == 0, "staged rows are whole 16-B pieces");
+#pragma unroll
+  for (int q = 0; q < KF / 4; q++) {
+    const float4 t = lds_ld16(row + 4 * q);
+    s[4 * q + 0] = t.x, s[4 * q + 1] = t.y, s[4 * q + 2] = t.z, s[4 * q + 3] = t.w;
+  }
+}
+template <int DEG>
+__device__ __forceinline__ void sh_eval(const float* s, float x, float y, float z, float* rgb, uint32_t& clamped) {
   clamped = 0;
 #pragma unroll
   for (int c = 0; c < 3; c++) {
@@ -84,23 +98,91 @@ __device__ __forceinline__ void sh_to_rgb(const float* __restrict__ sh, const fl
   }
 }
 
-// DEG = -1: colours precomputed by the caller
-// One Gaussian; returns the number of tiles it touches (0 when culled).
-// SPLIT: SH rows from g.shs (features_dc) + g.shs_rest when g.shs_rest is set (a uniform branch:
-// with both row loaders in the kernel the scheduler keeps the split loads where they are used, 91
-// VGPRs; a split-only instantiation hoists them, 130 VGPRs, 75 -> 97 us at C3)
-template <int DEG, bool SPLIT = false>
-__device__ __forceinline__ uint32_t preprocess_one(int i, const GaussianArgs& g, const CameraArgs& c,
-                                                   int* __restrict__ radii, float4* __restrict__ splat,
-                                                   float4* __restrict__ binrec, uint32_t& dbits,
-                                                   uint32_t* __restrict__ tiles, uint8_t* __restrict__ clamped,
-                                                   bool& culled_prefiltered) {
-  radii[i] = 0;
-  tiles[i] = 0;
-  const float px = g.means3D[3 * i + 0], py = g.means3D[3 * i + 1], pz = g.means3D[3 * i + 2];
+// Where preprocess_view finds the Gaussian's SH row:
+//   ROW_GLOBAL  its global row g.shs[i], loaded by the lane where it is used
+//   ROW_SPLIT   as ROW_GLOBAL, or features_dc + features_rest rows when g.shs_rest is set (a uniform
+//               branch: with both row loaders in the kernel the scheduler keeps the split loads where
+//               they are used, 91 VGPRs; a split-only instantiation hoists them, 130 VGPRs, 75 -> 97
+//               us at C3)
+//   ROW_LDS     the workgroup's rows staged in LDS (stage_sh_rows), read with whole 16-B LDS loads
+//   ROW_REGS    loaded once by preprocess_shared and held in registers
+enum RowSrc { ROW_GLOBAL = 0, ROW_SPLIT = 1, ROW_LDS = 2, ROW_REGS = 3 };
+
+// floats of an SH row of degree DEG (3 for DEG = -1: the precomputed colour)
+constexpr int sh_row_floats(int deg) { return deg < 0 ? 3 : 3 * (deg + 1) * (deg + 1); }
+
+// The camera-independent half of one Gaussian's preprocess: mean, 3D covariance, opacity and its
+// culling limit, and the colour source: the precomputed colour (DEG = -1), the coefficients
+// (ROW_REGS) or the staged row's address (ROW_LDS); a global row is addressed by i (sh_row_of).
+template <int DEG, int SRC>
+struct PreShared {
+  float px, py, pz;
+  float cov3[6];
+  float op, lim;
+  const float* row;  // ROW_LDS: the staged SH row (global rows are addressed where they are loaded, sh_row_of)
+  float s[(DEG < 0 || SRC == ROW_REGS) ? sh_row_floats(DEG) : 1];  // colour / coefficients held in registers
+};
+
+// SH -> RGB of Gaussian i from its global row(s), by the launch's layout.  A uniform branch around
+// load + evaluation: with only the loads in the branches the compiler merges them into 48 one-dword
+// loads through selected addresses (128 VGPRs in k_preprocess_split<3>).
+template <int DEG, int SRC>
+__device__ __forceinline__ void sh_rgb_of(int i, const GaussianArgs& g, float x, float y, float z, float* rgb,
+                                          uint32_t& clamped) {
+  float s[sh_row_floats(DEG)];
+  if (SRC == ROW_SPLIT && g.shs_rest) {
+    sh_row_load<DEG>(g.shs + (size_t)i * 3, g.shs_rest + (size_t)i * (g.M - 1) * 3, true, g.M, s);
+    sh_eval<DEG>(s, x, y, z, rgb, clamped);
+  } else {
+    sh_row_load<DEG>(g.shs + (size_t)i * g.M * 3, nullptr, false, g.M, s);
+    sh_eval<DEG>(s, x, y, z, rgb, clamped);
+  }
+}
+
+// lds_row: the lane's staged row (ROW_LDS only).  HOIST = false (the single-view kernels): the opacity
+// and its culling limit are left to preprocess_view, which takes them where they are stored, beside
+// the SH row's loads -- loaded here, ahead of the near cull, the opacity's latency is exposed on its
+// own (k_preprocess<3> at C3: 72 -> 91 us).
+template <int DEG, int SRC, bool HOIST>
+__device__ __forceinline__ PreShared<DEG, SRC> preprocess_shared(int i, const GaussianArgs& g, const float* lds_row) {
+  PreShared<DEG, SRC> sh;
+  sh.px = g.means3D[3 * i + 0], sh.py = g.means3D[3 * i + 1], sh.pz = g.means3D[3 * i + 2];
+  if (g.cov3D) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) sh.cov3[k] = g.cov3D[6 * i + k];
+  } else {
+    cov3d(g.scales[3 * i], g.scales[3 * i + 1], g.scales[3 * i + 2], g.scale_modifier, g.rotations[4 * i],
+          g.rotations[4 * i + 1], g.rotations[4 * i + 2], g.rotations[4 * i + 3], sh.cov3);
+  }
+  // culling limit of the {alpha >= 1/255} ellipse (render-side work skipping only; never
+  // changes a result, see ellipse_meets_rect): q(d) <= 2 ln(255 o), with safety margins
+  sh.op = HOIST ? g.opacities[i] : 0.0f;
+  sh.lim = HOIST ? cull_lim(sh.op) : 0.0f;
+  sh.row = lds_row, sh.s[0] = 0.0f;
+  if constexpr (DEG < 0) {
+    sh.s[0] = g.colors[3 * i], sh.s[1] = g.colors[3 * i + 1], sh.s[2] = g.colors[3 * i + 2];
+  } else if constexpr (SRC == ROW_REGS) {
+    sh_row_load<DEG>(g.shs + (size_t)i * g.M * 3, nullptr, false, g.M, sh.s);
+  }
+  return sh;
+}
+
+// What one camera adds for Gaussian i: near cull, projection, EWA cov2D -> conic, radius and tile
+// rectangle, SH -> RGB, the tile-exact row spans, and the stores of the view's outputs.  Returns the
+// number of tiles the Gaussian touches (0 when culled; radii[i] and tiles[i] are then 0).
+template <int DEG, int SRC, bool HOIST>
+__device__ __forceinline__ uint32_t preprocess_view(int i, const PreShared<DEG, SRC>& sh, const GaussianArgs& g,
+                                                    const CameraArgs& c,
+                                                    int* __restrict__ radii, float4* __restrict__ splat,
+                                                    float4* __restrict__ binrec, uint32_t& dbits,
+                                                    uint32_t* __restrict__ tiles, uint8_t* __restrict__ clamped,
+                                                    bool& culled_prefiltered) {
+  const float px = sh.px, py = sh.py, pz = sh.pz;
   const float3v pv = xf43(c.view, px, py, pz);
   if (pv.z <= 0.2f) {
     culled_prefiltered = c.prefiltered != 0;  // upstream raises "Point is filtered although prefiltered is set"
+    radii[i] = 0;
+    tiles[i] = 0;
     return 0;
   }
   const float* P = c.proj;
@@ -110,17 +192,13 @@ __device__ __forceinline__ uint32_t preprocess_one(int i, const GaussianArgs& g,
   const float pw = 1.0f / (hw + 0.0000001f);
   const float projx = hx * pw, projy = hy * pw;
 
-  float cov3[6];
-  if (g.cov3D) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) cov3[k] = g.cov3D[6 * i + k];
-  } else {
-    cov3d(g.scales[3 * i], g.scales[3 * i + 1], g.scales[3 * i + 2], g.scale_modifier, g.rotations[4 * i],
-          g.rotations[4 * i + 1], g.rotations[4 * i + 2], g.rotations[4 * i + 3], cov3);
-  }
-  const Cov2D cv = cov2d(c.view, px, py, pz, cov3, c.fx, c.fy, c.tanfovx, c.tanfovy);
+  const Cov2D cv = cov2d(c.view, px, py, pz, sh.cov3, c.fx, c.fy, c.tanfovx, c.tanfovy);
   const float det = cv.a * cv.c - cv.b * cv.b;
-  if (det == 0.0f) return 0;
+  if (det == 0.0f) {
+    radii[i] = 0;
+    tiles[i] = 0;
+    return 0;
+  }
   const float det_inv = 1.f / det;
   const float cxx = cv.c * det_inv, cxy = -cv.b * det_inv, cyy = cv.a * det_inv;
   const float mid = 0.5f * (cv.a + cv.c);
@@ -131,27 +209,31 @@ __device__ __forceinline__ uint32_t preprocess_one(int i, const GaussianArgs& g,
   int x0, y0, x1, y1;
   get_rect(sx, sy, radius, c.gx, c.gy, x0, y0, x1, y1);
   const int area = (x1 - x0) * (y1 - y0);
-  if (area == 0) return 0;
+  if (area == 0) {
+    radii[i] = 0;
+    tiles[i] = 0;
+    return 0;
+  }
 
   float rgb[3];
   uint32_t cl = 0;
-  if (DEG < 0) {
-    rgb[0] = g.colors[3 * i];
-    rgb[1] = g.colors[3 * i + 1];
-    rgb[2] = g.colors[3 * i + 2];
+  if constexpr (DEG < 0) {
+    rgb[0] = sh.s[0], rgb[1] = sh.s[1], rgb[2] = sh.s[2];
   } else {
     float dx = px - c.campos[0], dy = py - c.campos[1], dz = pz - c.campos[2];
     float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    if (SPLIT && g.shs_rest)
-      sh_to_rgb<(DEG < 0 ? 0 : DEG)>(g.shs + (size_t)i * 3, g.shs_rest + (size_t)i * (g.M - 1) * 3, g.M, dx / len,
-                                     dy / len, dz / len, rgb, cl);
-    else
-      sh_to_rgb<(DEG < 0 ? 0 : DEG)>(g.shs + (size_t)i * g.M * 3, nullptr, g.M, dx / len, dy / len, dz / len, rgb, cl);
+    if constexpr (SRC == ROW_REGS) {
+      sh_eval<DEG>(sh.s, dx / len, dy / len, dz / len, rgb, cl);
+    } else if constexpr (SRC == ROW_LDS) {
+      float s[sh_row_floats(DEG)];
+      sh_row_load_lds<DEG>(sh.row, s);
+      sh_eval<DEG>(s, dx / len, dy / len, dz / len, rgb, cl);
+    } else {
+      sh_rgb_of<DEG, SRC>(i, g, dx / len, dy / len, dz / len, rgb, cl);
+    }
   }
-  // culling limit of the {alpha >= 1/255} ellipse (render-side work skipping only; never
-  // changes a result, see ellipse_meets_rect): q(d) <= 2 ln(255 o), with safety margins
-  const float op = g.opacities[i];
-  const float lim = cull_lim(op);
+  const float op = HOIST ? sh.op : g.opacities[i];
+  const float lim = HOIST ? sh.lim : cull_lim(op);
   splat[3 * i + 0] = make_float4(sx, sy, cxx, cxy);
   splat[3 * i + 1] = make_float4(cyy, op, rgb[0], rgb[1]);
   splat[3 * i + 2] = make_float4(rgb[2], pv.z, lim, 0.0f);
@@ -199,42 +281,59 @@ __device__ __forceinline__ void workgroup_totals(uint32_t area, bool culled, WgT
   }
 }
 
+// ROW_LDS: the rows of workgroup b's Gaussians, staged into the launch's dynamic LDS
+// (sh_stage_bytes) with coalesced 16-B loads; returns the lane's row.  The loads are bounded by the
+// rows that exist (a partial last workgroup), and every lane of the workgroup reaches the barrier.
+template <int DEG>
+__device__ __forceinline__ const float* stage_block_rows(const GaussianArgs& g, int b) {
+  extern __shared__ __attribute__((aligned(16))) float s_sh_rows[];
+  constexpr int KF = sh_row_floats(DEG);
+  const int i0 = b * 256;
+  stage_sh_rows<KF>(g.shs + (size_t)i0 * KF, min(256, g.P - i0), s_sh_rows);
+  lds_barrier();
+  return s_sh_rows + (int)threadIdx.x * sh_stage_stride(KF);
+}
+
 // The workgroup's tile total (num_rendered, read back by the host right after the first depth-sort
 // histogram launch while the ordering kernels run) and its count of Gaussians with instances (V)
 // go to its WgTotals slot (workgroup_totals).  depth_key[i] is the depth's bits for those and
 // DEPTH_DROP for every other Gaussian: the first depth-sort pass drops them, which is the
 // visibility compaction.
+template <int DEG, int SRC>
+__device__ __forceinline__ void preprocess_block(const GaussianArgs& g, const CameraArgs& c, int* __restrict__ radii,
+                                                 float4* __restrict__ splat, float4* __restrict__ binrec,
+                                                 uint32_t* __restrict__ depth_key, uint32_t* __restrict__ tiles,
+                                                 uint8_t* __restrict__ clamped, WgTotals* __restrict__ wg) {
+  const int b = (int)blockIdx.x + g.blk0, i = b * 256 + (int)threadIdx.x;
+  uint32_t area = 0, dbits = 0;
+  bool culled = false;
+  if (i < g.P) {
+    const PreShared<DEG, SRC> sh = preprocess_shared<DEG, SRC, false>(i, g, nullptr);
+    area = preprocess_view<DEG, SRC, false>(i, sh, g, c, radii, splat, binrec, dbits, tiles, clamped, culled);
+    depth_key[i] = area ? dbits : DEPTH_DROP;
+  }
+  workgroup_totals(area, culled, wg, (uint32_t)b);
+}
+
 template <int DEG>
 __global__ __launch_bounds__(256) void k_preprocess(GaussianArgs g, CameraArgs c, int* __restrict__ radii,
                                                     float4* __restrict__ splat, float4* __restrict__ binrec,
                                                     uint32_t* __restrict__ depth_key,
                                                     uint32_t* __restrict__ tiles, uint8_t* __restrict__ clamped,
                                                     WgTotals* __restrict__ wg) {
-  const int b = (int)blockIdx.x + g.blk0, i = b * 256 + (int)threadIdx.x;
-  uint32_t area = 0, dbits = 0;
-  bool culled = false;
-  if (i < g.P) {
-    area = preprocess_one<DEG>(i, g, c, radii, splat, binrec, dbits, tiles, clamped, culled);
-    depth_key[i] = area ? dbits : DEPTH_DROP;
-  }
-  workgroup_totals(area, culled, wg, (uint32_t)b);
+  preprocess_block<DEG, ROW_GLOBAL>(g, c, radii, splat, binrec, depth_key, tiles, clamped, wg);
 }
 
-// The split-SH preprocess: k_preprocess's body with the split row loader (preprocess_one SPLIT).
+// The split-SH preprocess: k_preprocess's body with the split row loader (ROW_SPLIT).  Five waves
+// per SIMD asked for: degree 3 allocates 98 VGPRs without it (4 waves), 96 and no spill with it.
 template <int DEG>
-__global__ __launch_bounds__(256) void k_preprocess_split(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_preprocess_split(
     GaussianArgs g, CameraArgs c, int* __restrict__ radii, float4* __restrict__ splat, float4* __restrict__ binrec,
     uint32_t* __restrict__ depth_key, uint32_t* __restrict__ tiles, uint8_t* __restrict__ clamped,
     WgTotals* __restrict__ wg) {
-  const int b = (int)blockIdx.x + g.blk0, i = b * 256 + (int)threadIdx.x;
-  uint32_t area = 0, dbits = 0;
-  bool culled = false;
-  if (i < g.P) {
-    area = preprocess_one<DEG, true>(i, g, c, radii, splat, binrec, dbits, tiles, clamped, culled);
-    depth_key[i] = area ? dbits : DEPTH_DROP;
-  }
-  workgroup_totals(area, culled, wg, (uint32_t)b);
+  preprocess_block<DEG, ROW_SPLIT>(g, c, radii, splat, binrec, depth_key, tiles, clamped, wg);
 }
+
 
 // The preprocess grid, launched whole or -- with row waits installed on this thread
 // (gs_set_row_waits) -- in row chunks: before chunk k the stream waits for event k, and chunk k
@@ -309,20 +408,36 @@ void fwd_preprocess_grid(const GaussianArgs& g, const CameraArgs& c, int* radii,
   }
 }
 
-// K views in one launch: every lane runs the single-view preprocess of its Gaussian for each
-// camera in turn (preprocess_one, so each view's outputs are bit-identical to its own launch);
-// the Gaussian's inputs come from HBM once, the later views read them from the caches.  The
-// per-view workgroup totals go to each view's WgTotals slots as in k_preprocess.
-template <int DEG>
+// K views in one launch.  Every lane forms the camera-independent half of its Gaussian once
+// (preprocess_shared: mean, 3D covariance, opacity and culling limit, unconditionally -- a Gaussian
+// culled by one camera may be visible to the next) and then runs preprocess_view for each camera in
+// turn: the code of the single-view kernels, so each view's outputs are bit-identical to its own
+// launch.  The SH rows, by GS_PREVIEWS_ROWS (C3, 4 views, per launch; the parent reloaded every
+// input for every view: 223 us, 122 VGPRs, 4 waves per SIMD):
+//   2  (the build) loaded once per lane and held in registers across the views (ROW_REGS), every
+//      layout: 126 VGPRs at degree 3, 4 waves per SIMD, 165 us
+//   1  staged in LDS once per workgroup (ROW_LDS: coalesced 16-B loads; 93 VGPRs but 52 KB of LDS at
+//      degree 3, so 3 workgroups per CU), where sh_rows_stageable() holds; other layouts reload the
+//      row per view (ROW_GLOBAL, as the single-view kernel does): 177 us
+// The per-view workgroup totals go to each view's WgTotals slots as in k_preprocess; every lane of
+// the workgroup reaches both barriers of every view.
+#ifndef GS_PREVIEWS_ROWS
+#define GS_PREVIEWS_ROWS 2
+#endif
+template <int DEG, int SRC>
 __global__ __launch_bounds__(256) void k_preprocess_views(GaussianArgs g, PreViews pv) {
   const int b = (int)blockIdx.x + g.blk0, i = b * 256 + (int)threadIdx.x;
+  const float* lds_row = nullptr;
+  if constexpr (SRC == ROW_LDS) lds_row = stage_block_rows<DEG>(g, b);
+  PreShared<DEG, SRC> sh{};
+  if (i < g.P) sh = preprocess_shared<DEG, SRC, true>(i, g, lds_row);
   for (int v = 0; v < pv.K; v++) {
     const GeomPtrs& geo = pv.geo[v];
     uint32_t area = 0, dbits = 0;
     bool culled = false;
     if (i < g.P) {
-      area = preprocess_one<DEG>(i, g, pv.c[v], pv.radii[v], geo.splat, geo.binrec, dbits, geo.tiles, geo.clamped,
-                                 culled);
+      area = preprocess_view<DEG, SRC, true>(i, sh, g, pv.c[v], pv.radii[v], geo.splat, geo.binrec, dbits, geo.tiles,
+                                       geo.clamped, culled);
       geo.keys_a[i] = area ? dbits : DEPTH_DROP;
     }
     workgroup_totals(area, culled, geo.wg_tot, (uint32_t)b);
@@ -334,15 +449,28 @@ void fwd_preprocess_views(const GaussianArgs& g0, const PreViews& pv, hipStream_
   launch_row_chunks(g0, st, [&](const GaussianArgs& g, dim3 grid) {
     const dim3 block(256);
     if (g.colors) {
-      GS_LAUNCH("preprocess_views", k_preprocess_views<-1>, grid, block, 0, st, g, pv);
+      GS_LAUNCH("preprocess_views", (k_preprocess_views<-1, ROW_GLOBAL>), grid, block, 0, st, g, pv);
       return;
     }
-    switch (g.D) {
-      case 0: GS_LAUNCH("preprocess_views", k_preprocess_views<0>, grid, block, 0, st, g, pv); break;
-      case 1: GS_LAUNCH("preprocess_views", k_preprocess_views<1>, grid, block, 0, st, g, pv); break;
-      case 2: GS_LAUNCH("preprocess_views", k_preprocess_views<2>, grid, block, 0, st, g, pv); break;
-      default: GS_LAUNCH("preprocess_views", k_preprocess_views<3>, grid, block, 0, st, g, pv); break;
+#define GS_PRE_VIEWS(D, SRC, lds) \
+  GS_LAUNCH("preprocess_views", (k_preprocess_views<D, SRC>), grid, block, lds, st, g, pv)
+#if GS_PREVIEWS_ROWS == 1
+    if (sh_rows_stageable(g.D, g.M, g.shs)) {  // degrees 1 and 3
+      if (g.D == 1) GS_PRE_VIEWS(1, ROW_LDS, sh_stage_bytes(sh_row_floats(1)));
+      else GS_PRE_VIEWS(3, ROW_LDS, sh_stage_bytes(sh_row_floats(3)));
+      return;
     }
+    constexpr int SRC = ROW_GLOBAL;
+#else
+    constexpr int SRC = ROW_REGS;
+#endif
+    switch (g.D) {
+      case 0: GS_PRE_VIEWS(0, SRC, 0); break;
+      case 1: GS_PRE_VIEWS(1, SRC, 0); break;
+      case 2: GS_PRE_VIEWS(2, SRC, 0); break;
+      default: GS_PRE_VIEWS(3, SRC, 0); break;
+    }
+#undef GS_PRE_VIEWS
   });
 }
 

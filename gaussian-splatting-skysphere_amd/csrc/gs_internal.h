@@ -86,10 +86,44 @@ __device__ __forceinline__ float4 lds_ld16(const float* p) {
   asm volatile("" : "+v"(t));
   return make_float4(t.x, t.y, t.z, t.w);
 }
-constexpr int SH_STAGE_ROW = 52;
+// LDS row stride (floats) of staged rows of KF floats, KF a multiple of 4: an odd number of 16-B
+// pieces, so the lanes' 16-B reads of one piece index are conflict-free (48 -> 52, 12 -> 12)
+constexpr int sh_stage_stride(int kf) { return 4 * ((kf / 4) | 1); }
+constexpr size_t sh_stage_bytes(int kf) { return (size_t)256 * sh_stage_stride(kf) * sizeof(float); }
+constexpr int SH_STAGE_ROW = sh_stage_stride(48);
+// nG (<= 256) contiguous rows of KF floats at src (16-B aligned) -> s_rows, 16-B loads, every load
+// in flight before the LDS stores; nothing past the nG rows is read.  The caller puts a barrier after it.
+template <int KF>
+__device__ __forceinline__ void stage_sh_rows(const float* __restrict__ src, int nG, float* s_rows) {
+  static_assert(KF % 4 == 0, "rows of whole 16-B pieces");
+  constexpr int Q = KF / 4, ROW = sh_stage_stride(KF);
+  const int t = (int)threadIdx.x;
+  const float4* src4 = reinterpret_cast<const float4*>(src);
+  const int n4 = nG * Q;
+  float4 v[Q];
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    const int f = t + 256 * q;
+    v[q] = f < n4 ? src4[f] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    const int f = t + 256 * q;
+    if (f < n4) {
+      const int r = f / Q;
+      *reinterpret_cast<float4*>(&s_rows[r * ROW + 4 * (f - r * Q)]) = v[q];
+    }
+  }
+}
+// Launch condition of the forward preprocess kernels that stage their rows (k_preprocess_views in a
+// GS_PREVIEWS_ROWS=1 build): rows exactly as long as the degree needs (M = (D + 1)^2), whole 16-B pieces (3 M a multiple of
+// 4: degrees 1 and 3) and a 16-B aligned base; every other layout takes the per-lane loader.
+inline bool sh_rows_stageable(int D, int M, const void* shs) {
+  return shs && D >= 0 && D <= 3 && M == (D + 1) * (D + 1) && (3 * M) % 4 == 0 && (((uintptr_t)shs) & 15) == 0;
+}
 template <bool SPLIT>
 __device__ __forceinline__ void stage_sh_rows48(const GaussianArgs& g, int i0, int nG, float* s_rows) {
-  constexpr int KF = 48, Q = KF / 4;
+  constexpr int KF = 48;
   const int t = (int)threadIdx.x;
   if constexpr (SPLIT) {
     constexpr int RF = KF - 3, RQ = (256 * RF + 1023) / 1024;  // features_rest float4 per thread (12)
@@ -135,22 +169,7 @@ __device__ __forceinline__ void stage_sh_rows48(const GaussianArgs& g, int i0, i
       s_rows[r * SH_STAGE_ROW + (e - 3 * r)] = dc[e];
     }
   } else {
-    const float4* src4 = reinterpret_cast<const float4*>(g.shs + (size_t)i0 * KF);
-    const int n4 = nG * Q;
-    float4 v[Q];
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-      const int f = t + 256 * q;
-      v[q] = f < n4 ? src4[f] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-      const int f = t + 256 * q;
-      if (f < n4) {
-        const int r = f / Q;
-        *reinterpret_cast<float4*>(&s_rows[r * SH_STAGE_ROW + 4 * (f - r * Q)]) = v[q];
-      }
-    }
+    stage_sh_rows<KF>(g.shs + (size_t)i0 * KF, nG, s_rows);
   }
 }
 // launch condition of the staged kernels: degree 3, M == 16, 16-B aligned row bases

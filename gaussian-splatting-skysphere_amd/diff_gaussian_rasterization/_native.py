@@ -206,6 +206,7 @@ SIGNATURES = {
     ),
     "gs_debug_export_slots": (_c_i, [_c_i, _c_i, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gs_debug_set_scan_spin_limit": (ctypes.c_uint, [ctypes.c_uint]),
+    "gs_debug_sh_rows_staged": (_c_i, [_c_i, _c_i, _c_p]),
     "gs_profile_enable": (None, [_c_i]),
     "gs_profile_collect": (_c_i, []),
     "gs_profile_reset": (None, []),

@@ -689,6 +689,13 @@ int gs_debug_export(int P, int image_width, int image_height, long long num_rend
  * "look-back wait timed out" (gs_forward_render).  Returns the previous limit (default 1 << 22). */
 unsigned gs_debug_set_scan_spin_limit(unsigned limit);
 
+/* ---- test hook: eligibility of an SH layout for the K-view preprocess's LDS-staged row loader ----
+ * 1 for rows of exactly M = (D + 1)^2 coefficients that are whole 16-B pieces (3 M a multiple of
+ * 4) at a 16-B aligned `shs`, else 0.  A library built with -DGS_PREVIEWS_ROWS=1 launches
+ * gs_forward_preprocess_views(_bounded) by it; the default build holds every layout's rows in
+ * registers instead (csrc/gs_forward.hip).  No GPU call; `shs` is only inspected as an address. */
+int gs_debug_sh_rows_staged(int D, int M, const void* shs);
+
 /* ---- debug export of the raw tile-sorted instance slots (tests) ----
  * slots[num_rendered]: the depth-ordered instance slot of every entry of the tile-sorted list
  * (the backward writes entry k's gradient record at slots[k]); tile_cut[tiles]: 1 + the slot
