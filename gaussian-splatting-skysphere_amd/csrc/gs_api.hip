@@ -131,8 +131,9 @@ static CameraArgs make_camera(const float* bg, int W, int H, const float* view, 
   c.fx = (float)W / (2.0f * tanfovx);
   c.W = W;
   c.H = H;
-  c.gx = (W + GS_TILE - 1) / GS_TILE;
-  c.gy = (H + GS_TILE - 1) / GS_TILE;
+  // (64-bit: a size the checks below refuse must not overflow on the way to them)
+  c.gx = (int)(((long long)W + GS_TILE - 1) / GS_TILE);
+  c.gy = (int)(((long long)H + GS_TILE - 1) / GS_TILE);
   c.prefiltered = prefiltered;
   return c;
 }
@@ -140,6 +141,36 @@ static CameraArgs make_camera(const float* bg, int W, int H, const float* view, 
 // a camera that carries an image size only (the buffer layouts and the binning read nothing else)
 static CameraArgs size_camera(int W, int H) {
   return make_camera(nullptr, W, H, nullptr, nullptr, nullptr, 1.0f, 1.0f, 0);
+}
+
+// The image-size limits of include/gsrast.h, for a positive size.  GS_MAX_GRID_DIM: preprocess_view
+// packs a Gaussian's tile rectangle as x0 | x1 << 16, y0 | y1 << 16 with x1 <= gx, y1 <= gy (binrec,
+// read back by span_of).  GS_MAX_TILES: tile_finish keeps bucket << 22 | rank per tile (tile_brank),
+// k_tile_order reads the rank with & 0x3FFFFF, and a rank is below the tile count.  Within these the
+// int products gx * gy, the uint32 sched_words(tiles) = 2 tiles + 513, the render grid of
+// xcd_span(tiles) * 32 workgroups and tile_bits(tiles) <= 22 (three tile-sort passes) all hold; pixel
+// indices are size_t.
+static bool size_within_limits(int W, int H) {
+  const long long gx = ((long long)W + GS_TILE - 1) / GS_TILE, gy = ((long long)H + GS_TILE - 1) / GS_TILE;
+  return gx <= GS_MAX_GRID_DIM && gy <= GS_MAX_GRID_DIM && gx * gy <= (long long)GS_MAX_TILES;
+}
+#define GS_E_SIZE_LIMIT \
+  "image size %d x %d is too large: at most 65535 tiles of 16 pixels per row and per column and 4194304 tiles in all"
+// the check itself, behind each entry's positive-size check (the text after an entry's own prefix)
+static bool size_limit_error(int W, int H, const char* prefix = "") {
+  if (size_within_limits(W, H)) return false;
+  char fmt[256];
+  snprintf(fmt, sizeof(fmt), "%s%s", prefix, GS_E_SIZE_LIMIT);
+  set_error(fmt, W, H);
+  return true;
+}
+// the sizing queries: 0 bytes for such a size, the message left without failing the thread's next call
+static bool size_query_refused(int W, int H) {
+  if (W <= 0 || H <= 0 || size_within_limits(W, H)) return false;
+  char buf[256];
+  snprintf(buf, sizeof(buf), GS_E_SIZE_LIMIT, W, H);
+  t_err = buf;
+  return true;
 }
 
 // The scene of a call, packed once at the ABI boundary, in the entries' own argument order
@@ -155,6 +186,7 @@ static GaussianArgs make_scene(int P, int D, int M, const float* means3D, const 
 static bool validate(const GaussianArgs& g, const CameraArgs& c, bool need_opac = true) {
   if (g.P < 0) return set_error("P must be >= 0"), false;
   if (c.W <= 0 || c.H <= 0) return set_error("image size must be positive (got %d x %d)", c.W, c.H), false;
+  if (size_limit_error(c.W, c.H)) return false;
   if (g.P > 0) {
     if (!g.means3D || (need_opac && !g.opacities) || !c.view || !c.proj || !c.bg)
       return set_error("missing required input pointer"), false;
@@ -279,16 +311,21 @@ const char* gs_last_error(void) { return t_err.c_str(); }
 
 size_t gs_geom_buffer_bytes(int P) { return geom_layout((size_t)(P > 0 ? P : 1), nullptr, nullptr); }
 size_t gs_binning_buffer_bytes(long long num_rendered, int W, int H) {
+  if (size_query_refused(W, H)) return 0;
   int tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
   return bin_layout((size_t)(num_rendered > 0 ? num_rendered : 1), tiles, nullptr, nullptr);
 }
-size_t gs_image_buffer_bytes(int W, int H) { return img_layout(W, H, nullptr, nullptr); }
+size_t gs_image_buffer_bytes(int W, int H) {
+  if (size_query_refused(W, H)) return 0;
+  return img_layout(W, H, nullptr, nullptr);
+}
 long long gs_binning_layout_count(size_t bytes, int W, int H) {
   // every array of bin_layout has a size that never decreases with the count (sort_scratch_words
   // is a monotone bound, not sort_plan's nb), so gs_binning_buffer_bytes is non-decreasing, and two
   // counts with the same byte size have the same aligned array sizes, hence the same layout: the
   // largest count that fits `bytes` lays the buffer out exactly as the count it was sized for
   // (tests/test_abi.py checks this around the sort's block-count steps at k * 2^23 instances)
+  if (size_query_refused(W, H)) return 0;
   if (gs_binning_buffer_bytes(1, W, H) > bytes) return 0;
   long long lo = 1, hi = GS_MAX_INSTANCES;
   while (lo < hi) {
@@ -663,6 +700,7 @@ static int forward_render(int P, const CameraArgs& c, const FwdOut& o, unsigned 
   clear_error(debug);
   if (P <= 0) return 0;
   if (c.W <= 0 || c.H <= 0) return set_error("image size must be positive"), 1;
+  if (size_limit_error(c.W, c.H)) return 1;
   if (o.num_rendered < 0 || o.num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
   if (!o.geom || !o.binning || !o.image || !o.out_color || ((mode & TAIL_BIN) && !o.radii))
     return set_error("missing buffer pointer"), 1;
@@ -907,6 +945,7 @@ int gs_forward_bin_views(int K, int P, int W, int H, void* const* geom_buffer, c
   if (K <= 0 || K > FUSED_MAX_VIEWS) return set_error("views: 1 to 8 per call"), 1;
   if (P < 0) return set_error("P must be >= 0"), 1;
   if (W <= 0 || H <= 0) return set_error("image size must be positive"), 1;
+  if (size_limit_error(W, H)) return 1;
   if (!geom_buffer || !num_rendered || !binning_buffer || !image_buffer) return set_error("missing per-view array"), 1;
   if (P == 0) return 0;
   long long I = 0;
@@ -1218,6 +1257,7 @@ int gs_backward_render_aux(int P, int D, int M, const float* background, int W, 
   clear_error(debug);
   if (P < 0) return set_error("P must be >= 0"), 1;
   if (W <= 0 || H <= 0) return set_error("image size must be positive (got %d x %d)", W, H), 1;
+  if (size_limit_error(W, H)) return 1;
   if (P == 0) return 0;
   if (!viewmatrix || !projmatrix || !background) return set_error("missing required input pointer"), 1;
   const bool with_aux = dL_dout_invdepth || dL_dout_alpha;
@@ -1275,6 +1315,9 @@ static int backward_gaussians_impl(const GaussianArgs& scene, int first, int cou
     if (!w.viewmatrix || !w.projmatrix || !w.geom_buffer || (scene.shs && !w.campos))
       return set_error("view %d: missing pointer", v), 1;
     if (w.image_width <= 0 || w.image_height <= 0) return set_error("view %d: bad image size", v), 1;
+    char pre[32];
+    snprintf(pre, sizeof(pre), "view %d: ", v);
+    if (size_limit_error(w.image_width, w.image_height, pre)) return 1;
   }
   if (wait_event && !check_hip(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0), "hipStreamWaitEvent")) return 1;
   // the range [first, first + count) as a P = count problem: every per-Gaussian array is row-indexed,
@@ -1378,6 +1421,7 @@ int gs_backward_gaussians_adam_stats_aux(int P, int D, int M, const float* means
   if (!view->viewmatrix || !view->projmatrix || !view->campos || !view->geom_buffer)
     return set_error("view: missing pointer"), 1;
   if (view->image_width <= 0 || view->image_height <= 0) return set_error("view: bad image size"), 1;
+  if (size_limit_error(view->image_width, view->image_height, "view: ")) return 1;
   for (int k = 0; k < 6; k++) {
     if (!params_host[k] || !exp_avg_host[k] || !exp_avg_sq_host[k]) return set_error("missing tensor pointer"), 1;
     if (step_host[k] < 1) return set_error("adam: step must be >= 1"), 1;
@@ -1733,8 +1777,10 @@ int gs_debug_export(int P, int W, int H, long long num_rendered, const void* geo
                     void* stream) {
   clear_error(0);
   hipStream_t st = (hipStream_t)stream;
-  const int gx = (W + GS_TILE - 1) / GS_TILE, gy = (H + GS_TILE - 1) / GS_TILE;
   if (P <= 0) return 0;
+  if (W <= 0 || H <= 0) return set_error("debug_export: image size must be positive (got %d x %d)", W, H), 1;
+  if (size_limit_error(W, H, "debug_export: ")) return 1;
+  const int gx = (W + GS_TILE - 1) / GS_TILE, gy = (H + GS_TILE - 1) / GS_TILE;
   const Layouts L(P, num_rendered, size_camera(W, H), geom_buffer, binning_buffer, image_buffer);
   if (point_list && num_rendered > 0)
     GS_LAUNCH("export_list", k_export_list, dim3((unsigned)((num_rendered + 255) / 256)), dim3(256), 0, st,
@@ -1759,6 +1805,7 @@ int gs_debug_export_slots(int W, int H, long long num_rendered, const void* binn
   clear_error(0);
   hipStream_t st = (hipStream_t)stream;
   if (W <= 0 || H <= 0 || num_rendered < 0) return set_error("debug_export_slots: bad arguments"), 1;
+  if (size_limit_error(W, H, "debug_export_slots: ")) return 1;
   const int gx = (W + GS_TILE - 1) / GS_TILE, gy = (H + GS_TILE - 1) / GS_TILE;
   const Layouts L(0, num_rendered, size_camera(W, H), nullptr, binning_buffer, image_buffer);  // no geometry
   if (slots && num_rendered > 0)

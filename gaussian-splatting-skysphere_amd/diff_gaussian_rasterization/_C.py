@@ -41,6 +41,20 @@ def _load_ext():
 _EXT = _load_ext()
 
 
+def check_image_size(W, H):
+    """Raises for an image beyond the library's size limits (include/gsrast.h: GS_MAX_GRID_DIM,
+    GS_MAX_TILES), with the library's message: its sizing query returns 0 bytes for such a size."""
+    if (W, H) in _SIZES_OK:  # (a training loop asks about a handful of sizes, every iteration)
+        return
+    if W > 0 and H > 0 and _lib.gs_image_buffer_bytes(int(W), int(H)) == 0:
+        raise RuntimeError(f"rasterize_gaussians: {_native.last_error()}")
+    if len(_SIZES_OK) < 4096:
+        _SIZES_OK.add((W, H))
+
+
+_SIZES_OK = set()
+
+
 def _dev_check(t: torch.Tensor, name: str):
     if not t.is_cuda:
         raise RuntimeError(

@@ -554,6 +554,7 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        _C.check_image_size(s.image_width, s.image_height)
         empty = torch.Tensor([])
         shs = empty if shs is None else shs
         colors_precomp = empty if colors_precomp is None else colors_precomp

@@ -80,6 +80,23 @@ extern "C" {
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
+/* ---- image-size limits ----
+ * An image of W x H pixels is a grid of gx x gy tiles of 16 x 16 pixels, gx = ceil(W / 16),
+ * gy = ceil(H / 16).  Every entry that takes an image size (image_width / image_height arguments and
+ * the sizes inside gs_view_grad) refuses, before any device work and with a message in
+ * gs_last_error, a size with
+ *   gx > GS_MAX_GRID_DIM or gy > GS_MAX_GRID_DIM: a Gaussian's tile rectangle is kept as two 16-bit
+ *     halves per axis (x0 | x1 << 16 with x1 <= gx, likewise y), so W, H <= 1,048,560;
+ *   gx * gy > GS_MAX_TILES: a tile's rank in the backward's launch order is kept in 22 bits
+ *     (bucket << 22 | rank, rank < gx * gy).  Every narrower use lies within that: the tile sort's
+ *     keys (tile ids, at most 22 bits, three 8-bit-or-narrower passes), 32-bit tile and
+ *     scheduling-word counts (2 gx gy + 513) and the render grids (4 waves per tile); pixel counts
+ *     (at most 2^30) are 64-bit throughout.
+ * The sizing queries gs_binning_buffer_bytes, gs_image_buffer_bytes and gs_binning_layout_count
+ * return 0 for such a size (and leave the message in gs_last_error): no buffer fits it. */
+#define GS_MAX_GRID_DIM 65535
+#define GS_MAX_TILES (1 << 22)
+
 /* ---- scratch sizing (bytes) ---- */
 size_t gs_geom_buffer_bytes(int P);
 size_t gs_binning_buffer_bytes(long long num_rendered, int image_width, int image_height);

@@ -308,7 +308,8 @@ def tie_clones(n_pairs=2600, W=203, H=117):
     for half in range(2):
         for k in range(n_pairs):
             b.add_tile(k % b.tiles, 3.0, opacity=0.5, colour=cols[half * n_pairs + k])
-    return b.build(f"tie_clones_{2 * n_pairs}", props=dict(n_pairs=n_pairs))
+    name = f"tie_clones_{2 * n_pairs}" + ("" if (W, H) == (203, 117) else f"_{W}x{H}")
+    return b.build(name, props=dict(n_pairs=n_pairs))
 
 
 def reversed_scene(cs):
@@ -427,6 +428,53 @@ def big_owner(kind):
     return cs
 
 
+# Grids past 1080p (8,160 tiles, 13 tile bits): the tile sort's digit plan follows the bit count of
+# the tile count -- 14 bits 7 + 7, 15 bits 7 + 8, 16 bits 8 + 8, 17 bits 5 + 6 + 6 (the first
+# three-pass tile sort: the sorted list ends in the other ping-pong buffer).  (W, H, tile bits).
+LARGE_GRIDS = ((2059, 1013, 14), (2059, 2037, 15), (4107, 2037, 16), (4096, 4096, 16), (4107, 4085, 17))
+GRID17 = (4107, 4085)   # 257 x 256 = 65,792 tiles, ragged last column and row
+FEW_BIG_TILES = (0, 256, 65535, 65536, 65791)  # first tile, last of row 0, either side of 2^16, last
+
+
+def tile_sort_plan(tiles):
+    """Digit widths of the tile sort's passes, first pass first, restated from DESIGN.md: 8-bit
+    digits at most, as few passes as the bit count of the tile ids allows, (nearly) equal widths
+    with the narrower remainder first."""
+    bits = max(1, (tiles - 1).bit_length())
+    passes = -(-bits // 8)
+    width = -(-bits // passes)
+    first = bits - (passes - 1) * width
+    return [first] + [width] * (passes - 1)
+
+
+def few_big():
+    """17 tile bits, few Gaussians with very many instances: three full-screen Gaussians (65,792
+    instances each; depths 2, 3, 3: a tie) and five one-tile Gaussians at the tied depth in
+    FEW_BIG_TILES, four absent ones.  P = 12, I = 197,381: more than a duplicate block's 2048
+    slots per Gaussian on average, so the per-splat duplicate runs, and every owner's run is past
+    65,535 records."""
+    b = Builder(*GRID17, seed=17, bg=(0.05, 0.0, 0.1))
+    big = [b.add_all_tiles(z, op) for z, op in ((2.0, 0.05), (3.0, 0.07), (3.0, 0.09))]
+    for t in FEW_BIG_TILES:
+        b.add_tile(t, 3.0, opacity=0.4)
+    cs = b.build("few_big", shuffle=True, n_absent=4)
+    cs.props["big"] = [int(cs.props["index_of"][h]) for h in big]
+    return cs
+
+
+def owner_among_many():
+    """17 tile bits, balanced: one one-tile Gaussian per tile (depths cycling over three values) and
+    one full-screen Gaussian at the middle depth, 1000 absent.  P = 66,793, I = 131,584: the
+    look-back duplicate, where the one owner's 65,792 records cross 33 blocks of 2048 slots."""
+    b = Builder(*GRID17, seed=18, bg=(0.0, 0.05, 0.05))
+    for t in range(b.tiles):
+        b.add_tile(t, TIE_DEPTHS[t % 3], opacity=float(b.rng.uniform(0.2, 0.9)))
+    big = b.add_all_tiles(3.0, 0.05)
+    cs = b.build("owner_among_many", shuffle=True, n_absent=1000)
+    cs.props["big"] = [int(cs.props["index_of"][big])]
+    return cs
+
+
 def path_switch(P, W=203, H=117):
     """P Gaussians, all behind the camera except exactly 2049 one-tile Gaussians scattered through
     the index range (depths cycling over three values: ties).  Only the preprocess and the first
@@ -479,17 +527,23 @@ def oracle_scene(oracle, cam, sc, bg):
                         sh_degree=sc.sh_degree, scales=sc.scales.numpy(), rotations=sc.rotations.numpy())
 
 
+CACHE_MAX_PIXELS = 1920 * 1080  # larger forwards (up to 200 MB an array) are computed per use
+
+
 def oracle_forward(oracle, cs):
     """The oracle's forward with intermediates for a constructed scene, computed once per session
-    and shared (read-only) by the CPU and GPU tests of that scene."""
-    if cs.name not in _FORWARD_CACHE:
-        fw = oracle.forward(oracle_scene(oracle, cs.cam, cs.scene, cs.bg), intermediates=True)
-        fw["bg"] = cs.bg
-        for v in fw.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
+    and shared (read-only) by the CPU and GPU tests of that scene.  A forward above 1080p is not
+    kept: whoever asks computes it and lets it go."""
+    if cs.name in _FORWARD_CACHE:
+        return _FORWARD_CACHE[cs.name]
+    fw = oracle.forward(oracle_scene(oracle, cs.cam, cs.scene, cs.bg), intermediates=True)
+    fw["bg"] = cs.bg
+    for v in fw.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    if cs.cam.image_width * cs.cam.image_height <= CACHE_MAX_PIXELS:
         _FORWARD_CACHE[cs.name] = fw
-    return _FORWARD_CACHE[cs.name]
+    return fw
 
 
 _SCENE_CACHE: dict = {}
@@ -516,4 +570,7 @@ def all_scene_specs():
               ("stop_129_tail_elsewhere", stop_edge, (129, "tail_elsewhere"))]
     specs += [(f"big_owner_{k}", big_owner, (k,)) for k in ("straddle", "chunk_start", "pair")]
     specs += [(f"path_switch_{P}", path_switch, (P,)) for P in (LB_MAX_P, LB_MAX_P + 1)]
+    specs += [(f"one_per_tile_{W}x{H}", one_per_tile, (W, H)) for W, H, _ in LARGE_GRIDS]
+    specs += [("tie_clones_80000_4107x4085", tie_clones, (40000,) + GRID17), ("few_big", few_big, ()),
+              ("owner_among_many", owner_among_many, ())]
     return specs

@@ -474,7 +474,92 @@ def build_rows():
     return rows
 
 
+# The image-size limits (include/gsrast.h): gx = ceil(W / 16) and gy = ceil(H / 16) at most
+# GS_MAX_GRID_DIM = 65535 each, gx * gy at most GS_MAX_TILES = 2^22.  The last accepted and the first
+# refused value of each.
+W_LAST, W_FIRST = 65535 * 16, 65535 * 16 + 1          # gx = 65535 | 65536 (with H = 16: one tile row)
+SQ_LAST, SQ_FIRST = 2048 * 16, 2048 * 16 + 1          # 2048 x 2048 = 2^22 tiles | 2049 x 2048
+LIMIT_SIZES = [  # (W, H, accepted)
+    (W_LAST, 16, True), (W_FIRST, 16, False), (16, W_LAST, True), (16, W_FIRST, False),
+    (SQ_LAST, SQ_LAST, True), (SQ_FIRST, SQ_LAST, False), (SQ_LAST, SQ_FIRST, False),
+    (64 * 16, 65535 * 16, True), (64 * 16 + 1, 65535 * 16, False),   # 64 x 65535 < 2^22 < 65 x 65535
+    (0x7FFFFFFF, 16, False), (16, 0x7FFFFFFF, False), (0x7FFFFFFF, 0x7FFFFFFF, False),
+]
+
+
+def E_LIMIT(W, H, prefix=""):
+    return (f"{prefix}image size {W} x {H} is too large: at most 65535 tiles of 16 pixels per row and per column "
+            "and 4194304 tiles in all")
+
+
+def size_limit_rows():
+    """A table of its own (the ids of ROWS carry their index, and other tables are derived from
+    ROWS).  The limit check follows the positive-size check directly: a row with an accepted size
+    reaches the entry's next check, a refused one reports the limit in front of it."""
+    rows = []
+    fronts = [("gs_forward_preprocess", 0, 1), ("gs_forward_preprocess_split", 0, 1), ("gs_forward_bounded", None, 1),
+              ("gs_forward_counted", 0, 1), ("gs_rasterize_forward", None, -1), ("gs_backward", None, 1),
+              ("gs_backward_accumulate", None, 1), ("gs_backward_accumulate_aux", None, 1),
+              ("gs_backward_accumulate_split", None, 1)]
+    for e, nr, rc in fronts:  # validate(): P, positive size, the limits, pointers
+        for W, H, ok in LIMIT_SIZES:
+            rows.append((e, dict(W=W, H=H, means3D=None), rc, E_IN if ok else E_LIMIT(W, H), nr))
+        rows += [
+            (e, dict(P=-1, W=W_FIRST), rc, E_P, nr),
+            (e, dict(W=W_FIRST, H=0), rc, E_SIZE % (W_FIRST, 0), nr),
+            (e, dict(P=0, W=W_FIRST), rc, E_LIMIT(W_FIRST, 16), nr),      # also for an empty scene, as W = 0 is
+            (e, dict(P=0, W=W_LAST, means3D=None), 0, "", nr),
+        ]
+    for e in ("gs_forward_render", "gs_forward_render_bounded", "gs_forward_render_aux", "gs_forward_render_binned"):
+        for W, H, ok in LIMIT_SIZES:
+            rows.append((e, dict(W=W, H=H, num_rendered=-1), 1, E_NR if ok else E_LIMIT(W, H), None))
+        rows += [(e, dict(P=0, W=W_FIRST), 0, "", None), (e, dict(W=W_FIRST, H=0), 1, E_SIZE_SHORT, None)]
+    e = "gs_forward_bin_views"
+    for W, H, ok in LIMIT_SIZES:
+        rows.append((e, dict(W=W, H=H, geoms=None), 1, "missing per-view array" if ok else E_LIMIT(W, H), None))
+    rows += [(e, dict(P=-1, W=W_FIRST), 1, E_P, None), (e, dict(P=0, W=W_FIRST), 1, E_LIMIT(W_FIRST, 16), None)]
+    S = SENTINEL
+    e = "gs_forward_preprocess_views"
+    rows += [
+        (e, dict(Ws=ints(16, W_FIRST)), 1, E_LIMIT(W_FIRST, 16), [0, 0]),
+        (e, dict(Ws=ints(W_FIRST, 0)), 1, E_LIMIT(W_FIRST, 16), [0, S]),          # view 0 is checked first
+        (e, dict(Ws=ints(16, W_LAST), views_=ptrs(X, None)), 1, E_IN, [0, 0]),
+        (e, dict(Ws=ints(SQ_LAST, 16), Hs=ints(SQ_LAST, 16), means3D=None), 1, E_IN, [0, S]),
+        # view 0's pointers are checked before view 1's size
+        (e, dict(Ws=ints(16, SQ_LAST), Hs=ints(16, SQ_FIRST), means3D=None), 1, E_IN, [0, S]),
+        (e, dict(Ws=ints(16, SQ_LAST), Hs=ints(16, SQ_FIRST)), 1, E_LIMIT(SQ_LAST, SQ_FIRST), [0, 0]),
+    ]
+    e = "gs_forward_preprocess_views_bounded"
+    rows += [
+        (e, dict(Hs=ints(16, W_FIRST)), 1, E_LIMIT(16, W_FIRST), None),
+        (e, dict(Hs=ints(16, W_LAST), geoms=ptrs(X, None)), 1, E_OUT, None),
+    ]
+    e = "gs_backward_render"
+    for W, H, ok in LIMIT_SIZES:
+        rows.append((e, dict(W=W, H=H, view=None), 1, E_IN if ok else E_LIMIT(W, H), None))
+    rows += [(e, dict(P=-1, W=W_FIRST), 1, E_P, None), (e, dict(P=0, W=W_FIRST), 1, E_LIMIT(W_FIRST, 16), None)]
+    for e in ("gs_backward_gaussians", "gs_backward_gaussians_range"):
+        for W, H, ok in LIMIT_SIZES:
+            # an accepted size leaves the next fault (the unknown accumulate bits are checked before the
+            # views; so a NULL gradient pointer cannot follow them: use the second view's size)
+            vl = views(view(image_width=W, image_height=H), view(image_width=0))
+            rows.append((e, dict(num_views=2, view_list=vl), 1,
+                         "view 1: bad image size" if ok else E_LIMIT(W, H, "view 0: "), None))
+        rows += [
+            (e, dict(num_views=2, view_list=views(view(), view(image_width=SQ_FIRST, image_height=SQ_LAST))), 1,
+             E_LIMIT(SQ_FIRST, SQ_LAST, "view 1: "), None),
+            (e, dict(view_list=views(view(image_width=W_FIRST, campos=None))), 1, "view 0: missing pointer", None),
+        ]
+    for e in ("gs_backward_gaussians_adam", "gs_backward_gaussians_adam_stats"):
+        for W, H, ok in LIMIT_SIZES:
+            v1 = ctypes.pointer(view(image_width=W, image_height=H))
+            rows.append((e, dict(view1=v1, steps=lls(1, 1, 0, 1, 1, 1)), 1,
+                         "adam: step must be >= 1" if ok else E_LIMIT(W, H, "view: "), None))
+    return rows
+
+
 ROWS = build_rows()
+LIMIT_ROWS = size_limit_rows()
 
 
 def _id(i, row):
@@ -523,3 +608,62 @@ def test_early_return(row):
     entry, over, rc, text, left = row
     got = call(entry, over)
     assert got == (rc, text, left), (entry, over)
+
+
+@pytest.mark.parametrize("row", LIMIT_ROWS, ids=[_id(i, r) for i, r in enumerate(LIMIT_ROWS)])
+def test_image_size_limits(row):
+    entry, over, rc, text, left = row
+    got = call(entry, over)
+    assert got == (rc, text, left), (entry, over)
+
+
+def test_image_size_limit_rows_cover_every_entry_with_a_size():
+    with_size = {e for e, names in PARAMS.items() if {"W", "Ws", "view_list", "view1"} & set(names.split())}
+    assert {r[0] for r in LIMIT_ROWS} == with_size == set(PARAMS)
+    for W, H, ok in LIMIT_SIZES:  # the table's own arithmetic, from the limits as documented
+        gx, gy = -(-W // 16), -(-H // 16)
+        assert ok == (gx <= 65535 and gy <= 65535 and gx * gy <= 1 << 22), (W, H)
+
+
+def test_sizing_queries_return_zero_past_the_limits():
+    """gs_image_buffer_bytes, gs_binning_buffer_bytes and gs_binning_layout_count agree with the
+    entries: a size the entries refuse has no buffer size (0, the message in gs_last_error), the
+    last accepted size has one, and a refused query does not fail the thread's next call."""
+    lib = _native.load()
+    for W, H, ok in LIMIT_SIZES:
+        img, binb = lib.gs_image_buffer_bytes(W, H), lib.gs_binning_buffer_bytes(1000, W, H)
+        if ok:
+            assert img >= 8 * W * H and binb >= 20 * 1000, (W, H)
+            assert lib.gs_binning_layout_count(binb, W, H) >= 1000
+        else:
+            assert img == 0 and binb == 0 and lib.gs_binning_layout_count(1 << 40, W, H) == 0, (W, H)
+            assert lib.gs_last_error().decode() == E_LIMIT(W, H)
+            assert call("gs_forward_render", dict(P=0)) == (0, "", None)  # the next call starts clean
+    # 17 tile bits and a non-positive size: as before
+    assert lib.gs_image_buffer_bytes(4107, 4085) >= 8 * 4107 * 4085
+    assert lib.gs_image_buffer_bytes(0, 16) > 0
+
+
+def test_rasterizer_refuses_an_oversized_image_before_the_device():
+    """Through GaussianRasterizer: the library's message, raised before any tensor is looked at
+    (host tensors here, which an accepted size rejects as such)."""
+    import torch
+
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+
+    def rast(W, H):
+        eye = torch.eye(4)
+        return GaussianRasterizer(GaussianRasterizationSettings(
+            image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, bg=torch.zeros(3), scale_modifier=1.0,
+            viewmatrix=eye, projmatrix=eye, sh_degree=0, campos=torch.zeros(3), prefiltered=False, debug=False))
+
+    m = torch.zeros((2, 3))
+    kw = dict(means3D=m, means2D=m, opacities=torch.ones(2, 1), colors_precomp=m, scales=m, rotations=torch.zeros(2, 4))
+    import re
+
+    with pytest.raises(RuntimeError, match=re.escape(E_LIMIT(SQ_FIRST, SQ_LAST))):
+        rast(SQ_FIRST, SQ_LAST)(**kw)
+    with pytest.raises(RuntimeError, match=re.escape(E_LIMIT(16, W_FIRST))):
+        rast(16, W_FIRST)(**kw)
+    with pytest.raises(RuntimeError, match="no CPU rasterizer"):
+        rast(SQ_LAST, SQ_LAST)(**kw)

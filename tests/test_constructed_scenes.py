@@ -15,11 +15,11 @@ SPECS = cs_mod.all_scene_specs()
 
 
 def _tile_max(n_contrib, gx, gy):
-    out = np.zeros(gx * gy, np.int64)
-    for t in range(gx * gy):
-        ty, tx = divmod(t, gx)
-        out[t] = n_contrib[TILE * ty:TILE * ty + TILE, TILE * tx:TILE * tx + TILE].max(initial=0)
-    return out
+    """Largest n_contrib of every tile (the ragged last column / row padded with 0)."""
+    H, W = n_contrib.shape
+    full = np.zeros((gy * TILE, gx * TILE), np.int64)
+    full[:H, :W] = n_contrib
+    return full.reshape(gy, TILE, gx, TILE).max(axis=(1, 3)).reshape(-1)
 
 
 def _owner_layout(fw):
@@ -102,6 +102,57 @@ def test_one_per_tile(oracle, W, H, bits):
     assert fw["num_rendered"] == tiles and (fw["ranges"][:, 1] - fw["ranges"][:, 0] == 1).all()
     assert (tiles - 1).bit_length() == bits  # 8 bits: one tile-sort pass; 9: two
     assert len(np.unique(fw["depth"][fw["tiles_touched"] > 0])) == 1
+
+
+PLANS = {14: [7, 7], 15: [7, 8], 16: [8, 8], 17: [5, 6, 6]}  # tile bits -> digit widths, first pass first
+
+
+@pytest.mark.parametrize("W,H,bits", cs_mod.LARGE_GRIDS)
+def test_large_grids_reach_the_later_pass_plans(W, H, bits):
+    """The grids above 1080p: the bit count of the tile ids and the tile sort's digit plan it
+    selects, restated here in plain Python (nothing imported from the library).  An odd number of
+    passes leaves the sorted list in the second ping-pong buffer: one pass (<= 8 bits) and the
+    three passes of 17 bits.  The promises themselves are checked by test_promised_counts_hold."""
+    cs = cached(cs_mod.one_per_tile, W, H)
+    gx, gy = cs_mod.grid(W, H)
+    tiles = gx * gy
+    assert len(cs.list_len) == tiles and cs.I == cs.V == tiles and (cs.list_len == 1).all()
+    assert (tiles - 1).bit_length() == bits
+    assert len(np.unique(cs.depth_bits[cs.tiles_touched > 0])) == 1
+    plan = cs_mod.tile_sort_plan(tiles)
+    assert plan == PLANS[bits] and sum(plan) == bits and max(plan) <= 8
+    assert (len(plan) % 2 == 1) == (bits == 17)
+    assert {(203, 117): [7], (256, 256): [8], (272, 256): [4, 5], (1920, 1080): [6, 7]} == {
+        wh: cs_mod.tile_sort_plan(cs_mod.grid(*wh)[0] * cs_mod.grid(*wh)[1])
+        for wh in ((203, 117), (256, 256), (272, 256), (1920, 1080))}
+    if (W, H) == (4096, 4096):
+        assert tiles == 1 << 16 and W % TILE == 0 and H % TILE == 0  # the last two-pass size, no ragged edge
+    if (W, H) == cs_mod.GRID17:
+        assert (gx, gy, tiles) == (257, 256, 65792) and W % TILE and H % TILE
+
+
+def test_seventeen_bit_scenes():
+    """What the three 17-bit scenes besides one_per_tile exist for (facts of the construction)."""
+    tiles = 65792
+    t = cached(cs_mod.tie_clones, 40000, *cs_mod.GRID17)
+    assert t.I == t.V == t.P == 80000 and len(np.unique(t.depth_bits)) == 1
+    # a clone pair in each of the first 40,000 tiles: tile ids that differ in all three digits
+    assert (t.list_len[:40000] == 2).all() and not t.list_len[40000:].any() and 40000 > 1 << (5 + 6)
+    assert np.array_equal(t.point_list[:2], [0, 40000])    # the tie resolves by index
+    f = cached(cs_mod.few_big)
+    assert (f.P, f.I, f.V) == (12, 197381, 8) and f.I == 3 * tiles + 5
+    assert f.I > DUP_SLOTS * f.P                           # unbalanced: the per-splat duplicate
+    big = f.props["big"]
+    assert (f.tiles_touched[big] == tiles).all() and tiles > 65535
+    assert sorted(f.list_len[list(cs_mod.FEW_BIG_TILES)]) == [4] * 5 and (f.list_len >= 3).all()
+    assert f.sorted_gid[0] == big[0] and len(np.unique(f.depth_bits[f.sorted_gid[1:]])) == 1
+    assert len(f.props["absent"]) == 4
+    o = cached(cs_mod.owner_among_many)
+    assert (o.P, o.I, o.V) == (66793, 131584, tiles + 1) and o.I <= DUP_SLOTS * o.P  # balanced: k_duplicate_lb
+    a, b = o.run(o.props["big"][0])
+    assert b - a == tiles and (b - 1) // DUP_SLOTS - a // DUP_SLOTS + 1 == 33  # 33 duplicate blocks
+    assert (o.list_len == 2).all() and len(np.unique(o.depth_bits[o.tiles_touched > 0])) == 3
+    assert len(o.props["absent"]) == 1000
 
 
 def test_tie_clones_span_sort_tiles_and_decide_the_image(oracle):

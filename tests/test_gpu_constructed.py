@@ -218,6 +218,104 @@ def test_prepared_views_with_different_exact_counts(oracle, device):
 
 
 # ------------------------------------------------------------------------------------------
+# grids above 1080p: the tile sort's later pass plans
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W,H,bits", cs_mod.LARGE_GRIDS)
+def test_one_instance_per_tile_above_1080p(oracle, device, W, H, bits):
+    """test_one_instance_per_tile continued past 1080p (8,160 tiles, 13 tile bits, 6 + 7): 8,256 tiles
+    = 14 bits sorted as 7 + 7, 16,512 = 15 bits as 7 + 8, 32,896 and 65,536 (exactly 2^16, no ragged
+    edge) = 16 bits as 8 + 8, and 65,792 = 17 bits, the first three-pass tile sort (5 + 6 + 6), whose
+    sorted list ends in the other ping-pong buffer (bin_layout's host-side parity against
+    radix_sort_pairs' own), with k_duplicate_lb counting the 5-bit first digit.  k_ranges,
+    k_tile_order and the scheduling words run over up to 8 times the tiles of 1080p.
+    MI355X: ratio 0.016 (dscales, 4107 x 2037)."""
+    _parity(oracle, device, cached(cs_mod.one_per_tile, W, H))
+
+
+def test_ties_through_three_tile_sort_passes(oracle, device):
+    """80,000 Gaussians with one depth bit pattern on the 17-bit grid (4107 x 4085), as clone pairs in
+    the first 40,000 tiles: the tile sort alone orders the list, so the (tile, index) order -- and the
+    image, which the clones' colour order decides -- needs all three passes (5 + 6 + 6) to be
+    stable across 40 sort tiles.  MI355X: ratio 0.013 (dscales)."""
+    _parity(oracle, device, cached(cs_mod.tie_clones, 40000, *cs_mod.GRID17))
+
+
+def test_owners_past_65535_records_per_splat_duplicate(oracle, device):
+    """few_big on the 17-bit grid: three full-screen Gaussians of 65,792 instances each (two at one
+    depth) and five one-tile ones in tiles 0, 256, 65535, 65536, 65791; P = 12, I = 197,381, so
+    dup_balanced is false and the per-splat k_duplicate writes owners' runs longer than 65,535
+    records, followed by the three-pass tile sort without the duplicate's first-digit counts.
+    MI355X: ratio 0.030 (dmeans3D)."""
+    _parity(oracle, device, cached(cs_mod.few_big))
+
+
+def test_owner_past_65535_records_lookback_duplicate(oracle, device):
+    """owner_among_many on the 17-bit grid: a one-tile Gaussian in every tile and one full-screen
+    Gaussian among them; P = 66,793, I = 131,584 (balanced), so k_duplicate_lb runs and the one
+    owner's 65,792 records cross 33 duplicate blocks (each finds the row segment that began before
+    its first slot), with the first digit counted under the 5-bit mask.
+    MI355X: ratio 0.014 (dmeans3D)."""
+    _parity(oracle, device, cached(cs_mod.owner_among_many))
+
+
+def test_prepared_views_three_pass_batched_sort(oracle, device):
+    """Two prepared views of the 4107 x 4085 one_per_tile scene (17 tile bits): the batched tile sort
+    (views = 2, every array one view stride apart) goes through three passes and both views' lists
+    end in the second ping-pong buffer.  Camera B is the identity camera moved right by 16 * 3 / fx:
+    every Gaussian (all at z = 3) moves one whole tile to the left, tile column 0 leaves the image,
+    I = 65,792 in A and 65,536 = 2^16 in B.  Each view is bit-equal to its single-view call (image,
+    radii, gradients) and to the oracle (image, radii, every intermediate), the gradients at the
+    contract against the oracle.  MI355X: ratio 0.014 (dscales, view B)."""
+    from diff_gaussian_rasterization import GaussianRasterizer, prepare_views
+
+    W, H = cs_mod.GRID17
+    cs = cached(cs_mod.one_per_tile, W, H)
+    gx, gy = cs_mod.grid(W, H)
+    sc, bg = cs.scene, cs.bg
+    fx = W / (2.0 * np.tan(cs.cam.FoVx / 2))
+    cam_b = gs_scenes.make_camera(np.eye(3), np.array([-cs_mod.TILE * 3.0 / fx, 0.0, 0.0]), W, H)
+    cams = [cs.cam, cam_b]
+    dpix = gs_scenes.dl_dimage(H, W, seed=5, scale=1.0).numpy()
+    d = sc.to(device)
+    rasts = [GaussianRasterizer(gs_scenes.raster_settings_for(c, 0, bg=torch.tensor(bg, device=device), device=device))
+             for c in cams]
+    names = ("means3D", "shs", "opacities", "scales", "rotations")
+    lv = {k: getattr(d, k).clone().requires_grad_(True) for k in names}
+    pre = prepare_views(rasts, lv["means3D"], lv["opacities"], shs=lv["shs"], scales=lv["scales"],
+                        rotations=lv["rotations"])
+    for v, (cam, r, p, I) in enumerate(zip(cams, rasts, pre, (gx * gy, (gx - 1) * gy))):
+        m2 = torch.zeros_like(lv["means3D"], requires_grad=True)
+        img, radii = r(means3D=lv["means3D"], means2D=m2, opacities=lv["opacities"], shs=lv["shs"],
+                       scales=lv["scales"], rotations=lv["rotations"], prepared=p)
+        (img * torch.tensor(dpix, device=device)).sum().backward()
+        torch.cuda.synchronize()
+        got = {k: types.SimpleNamespace(grad=t.grad.clone()) for k, t in lv.items()}
+        got["means2D"] = types.SimpleNamespace(grad=m2.grad.clone())
+        for t in lv.values():
+            t.grad = None
+        osc = _oracle_scene(oracle, cam, sc, bg)
+        ofw = oracle.forward(osc, intermediates=True)
+        ofw["bg"] = bg
+        assert ofw["num_rendered"] == I
+        assert (ofw["ranges"][:, 1].astype(np.int64) - ofw["ranges"][:, 0] ==
+                (np.arange(gx * gy) % gx < gx - v).astype(np.int64)).all()
+        np.testing.assert_array_equal(img.detach().cpu().numpy(), ofw["color"])
+        np.testing.assert_array_equal(radii.cpu().numpy(), ofw["radii"])
+        _check_forward_exact(ofw, cam, sc, device)
+        del ofw
+        img1, radii1, single = _gpu_run(cam, sc, device, bg, dpix)
+        assert torch.equal(img1, img) and torch.equal(radii1, radii)
+        for k in got:
+            assert torch.equal(single[k].grad, got[k].grad), (v, k)
+        del img1, single, img
+        gr = oracle.backward(osc, dpix)
+        ratio, where = _worst_ratio(got, gr)
+        print(f"\n[constructed three_pass_views {'AB'[v]}] I={I}: worst gradient / bound {ratio:.3f} ({where})")
+        _check_backward(gr, got)
+        _check_chain_noise(got, gr, oracle.backward_f32_acc(osc, dpix))
+
+
+# ------------------------------------------------------------------------------------------
 # distCUDA2 at its own boundaries
 # ------------------------------------------------------------------------------------------
 def _knn_check(oracle, device, pts):

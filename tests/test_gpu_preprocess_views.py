@@ -239,3 +239,125 @@ def test_row_waits_inside_a_workgroup(device):
     ev.record()
     torch.cuda.synchronize()
     _assert_equal_paths(_settings(_cams(3), 3, device), inp, 3, device, waits=[(0, 300, ev), (300, 2999, ev)])
+
+
+# ------------------------------------------------------------------------------------------
+# views of different sizes
+# ------------------------------------------------------------------------------------------
+# The bridges (_C.preprocess_views and its twin in gs_torch_ext.cpp) batch the K views' binning only
+# when every view has one W x H; otherwise each view bins itself inside its own prepared render,
+# behind the shared preprocess (k_preprocess_views with per-view gx, gy) and ordering.
+# Every comparison below is bit for bit (torch.equal): there is no bound, the gradient-to-bound
+# ratio of these tests is 0 by assertion (MI355X: all equal).
+MIXED_SIZES = {
+    # 256 tiles = 8 tile bits (one tile-sort pass), 272 tiles = 9 bits (two passes), and a ragged 5 x 3 grid
+    "three_sort_plans": [(256, 256), (272, 256), (70, 45)],
+    "one_tile_and_many": [(16, 16), (203, 117)],
+    "portrait_landscape": [(117, 203), (203, 117)],
+    # only the last of the launch's maximum of 8 views differs
+    "last_of_eight": [(70, 45)] * 7 + [(45, 70)],
+}
+
+
+def _mixed_cams(sizes):
+    """View k has the k-th pose of _cams at its own image size (the poses do not depend on the size)."""
+    return [_cams(k + 1, w, h)[k] for k, (w, h) in enumerate(sizes)]
+
+
+def _mixed_scene(sizes, P, deg, seed):
+    """Fills the frustum of the narrowest half-angles among the views, so every view sees it."""
+    w, h = min(sizes, key=lambda s: s[0] / s[1])  # the narrowest horizontal field (fovy is fixed)
+    return _scene(P, deg, seed=seed, cam=gs_scenes.identity_camera(w, h))
+
+
+@pytest.fixture(params=["ext", "ctypes"])
+def bridge(request, monkeypatch):
+    """Both implementations of preprocess_views / the prepared render: the torch C++ binding (the
+    default path) and the ctypes one (_C._EXT patched away, as tests/test_gpu_ext.py does)."""
+    from diff_gaussian_rasterization import _C
+
+    if request.param == "ext":
+        assert _C._EXT is not None, "the torch C++ host path (_gs_ext) is not loaded"
+    else:
+        monkeypatch.setattr(_C, "_EXT", None)
+    return request.param
+
+
+@pytest.mark.parametrize("deg", [1, 3])
+@pytest.mark.parametrize("name", list(MIXED_SIZES))
+def test_views_of_different_sizes(device, bridge, name, deg):
+    """Unequal image sizes in one prepare_views call, through both bridges: every view bit-equal to
+    its plain single-view call (images, radii, every debug_export field, every gradient)."""
+    sizes = MIXED_SIZES[name]
+    assert len(set(sizes)) > 1
+    inp = _inputs(_mixed_scene(sizes, 2999, deg, seed=31), device)
+    radii = _assert_equal_paths(_settings(_mixed_cams(sizes), deg, device), inp, deg, device)
+    assert all((r > 0).any() for r in radii)
+
+
+def test_views_of_different_sizes_precomputed_colors(device, bridge):
+    """colors_precomp (no SH rows to share) with three sizes."""
+    sizes = MIXED_SIZES["three_sort_plans"]
+    d = _mixed_scene(sizes, 1500, 0, seed=33).to(device)
+    colors = torch.rand((d.P, 3), generator=torch.Generator().manual_seed(4)).to(device)
+    inp = dict(means3D=d.means3D, opacities=d.opacities, colors_precomp=colors, scales=d.scales, rotations=d.rotations)
+    radii = _assert_equal_paths(_settings(_mixed_cams(sizes), 0, device), inp, 0, device)
+    assert all((r > 0).any() for r in radii)
+
+
+def test_views_of_different_sizes_bounded(device, bridge):
+    """Unequal sizes with the prepared views bounded (binning_capacity=): each view sizes its own
+    binning buffer for the capacity and its own grid."""
+    sizes = MIXED_SIZES["three_sort_plans"]
+    inp = _inputs(_mixed_scene(sizes, 2999, 3, seed=35), device)
+    radii = _assert_equal_paths(_settings(_mixed_cams(sizes), 3, device), inp, 3, device, capacity=200_000)
+    assert all((r > 0).any() for r in radii)
+
+
+def test_views_of_different_sizes_row_waits(device):
+    """Unequal sizes with row waits installed, the chunk boundary inside a workgroup."""
+    sizes = MIXED_SIZES["portrait_landscape"]
+    inp = _inputs(_mixed_scene(sizes, 2999, 3, seed=37), device)
+    ev = torch.cuda.Event()
+    ev.record()
+    torch.cuda.synchronize()
+    radii = _assert_equal_paths(_settings(_mixed_cams(sizes), 3, device), inp, 3, device,
+                                waits=[(0, 300, ev), (300, 2999, ev)])
+    assert all((r > 0).any() for r in radii)
+
+
+@pytest.mark.parametrize("deg", [1, 3])
+def test_unbatched_fallback_equals_batched_binning(device, monkeypatch, deg):
+    """The same-size control: three views of one size through the ctypes bridge, binned together (the
+    default) and -- GSRAST_BATCH_VIEWS=0, which that bridge reads at every call -- each inside its
+    own prepared render, the path views of unequal sizes take.  Bit for bit the same buffers and
+    gradients, and both equal to the plain calls."""
+    from diff_gaussian_rasterization import _C
+
+    monkeypatch.setattr(_C, "_EXT", None)
+    ss = _settings(_cams(3), deg, device)
+    inp = _inputs(_scene(2999, deg, seed=39), device)
+    dpix = [gs_scenes.dl_dimage(H, W, seed=60 + v, scale=1.0).to(device) for v in range(3)]
+    monkeypatch.delenv("GSRAST_BATCH_VIEWS", raising=False)
+    batched = _buffers(ss, inp, deg, True)
+    b_out, b_grad = _autograd(ss, inp, dpix, True)
+    monkeypatch.setenv("GSRAST_BATCH_VIEWS", "0")
+    single = _buffers(ss, inp, deg, True)
+    s_out, s_grad = _autograd(ss, inp, dpix, True)
+    radii = _assert_equal_paths(ss, inp, deg, device)  # the fallback against the plain calls
+    assert all((r > 0).any() for r in radii)
+    counts = [n for n, _, _, _ in single]
+    assert len(set(counts)) > 1                              # each view kept its own count: not batched
+    assert all(n == max(counts) for n, _, _, _ in batched)  # binned together: the largest count for all
+    for v, ((nb, cb, rb, eb), (ns, cs, rs, es)) in enumerate(zip(batched, single)):
+        assert torch.equal(cb, cs) and torch.equal(rb, rs), v
+        vis = rs > 0
+        for k in ("xy", "conic_opacity", "rgb", "depth"):
+            assert torch.equal(eb[k][vis], es[k][vis]), (v, k)
+        for k in ("tiles_touched", "ranges", "final_T", "n_contrib"):
+            assert torch.equal(eb[k], es[k]), (v, k)
+        assert torch.equal(eb["point_list"][:ns], es["point_list"]), v
+    for v, (b, s) in enumerate(zip(b_out, s_out)):
+        assert all(torch.equal(x, y) for x, y in zip(b, s)), v
+    for k in b_grad:
+        assert torch.equal(b_grad[k], s_grad[k]), k

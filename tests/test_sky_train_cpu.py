@@ -97,7 +97,20 @@ def _adam_rows():
     return rows
 
 
-ROWS = _render_rows() + _adam_rows()
+def _size_limit_rows():
+    """The image-size limits (tests/test_api_contract_cpu.py) in the two aux entries, after every
+    earlier row: the last accepted and the first refused size."""
+    r, a = "gs_backward_render_aux", "gs_backward_gaussians_adam_stats_aux"
+    v = lambda W, H: ctypes.pointer(tc.view(image_width=W, image_height=H))  # noqa: E731
+    rows = []
+    for W, H, ok in tc.LIMIT_SIZES:
+        rows.append((r, dict(W=W, H=H, view=None), 1, tc.E_IN if ok else tc.E_LIMIT(W, H)))
+        rows.append((a, dict(view1=v(W, H), steps=tc.lls(1, 1, 0, 1, 1, 1)), 1,
+                     "adam: step must be >= 1" if ok else tc.E_LIMIT(W, H, "view: ")))
+    return rows
+
+
+ROWS = _render_rows() + _adam_rows() + _size_limit_rows()
 
 
 def _id(i, row):
