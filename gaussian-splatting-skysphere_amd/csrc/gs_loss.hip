@@ -13,7 +13,9 @@
 //   S = (2 m1 m2 + C1)(2 s12 + C2) / ((m1^2 + m2^2 + C1)(s11 + s22 + C2)),
 //   s11 = E[x^2] - m1^2, s22 = E[y^2] - m2^2, s12 = E[xy] - m1 m2
 //   dS/dm1 = 2 m2 (A2 - A1) / (B1 B2) - 2 m1 S (1/B1 - 1/B2),  dS/dE[x^2] = -S / B2,
-//   dS/dE[xy] = 2 A1 / (B1 B2)
+//   dS/dE[xy] = 2 A1 / (B1 B2); with R1 = A1 / B1, R2 = A2 / B2 (S = R1 R2) evaluated as
+//   dS/dm1 = 2 R2 (m2 - m1 R1) / B1 + 2 R1 (m1 R2 - m2) / B2, every term of which is exactly 0
+//   where the image equals the target
 //   dL/dx(q) = scale * [ (w * dS/dm1)(q) + 2 x(q) (w * dS/dE[x^2])(q) + y(q) (w * dS/dE[xy])(q) ]
 //
 // The sums are reduced per workgroup and then per plane (or over all planes, k_loss_finish) in a
@@ -194,14 +196,23 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, SsimWin win, con
     const float mu12 = m1 * m2;
     const float A1 = 2.f * mu12 + C1, A2 = 2.f * (e12 - mu12) + C2;
     const float B1 = m1 * m1 + m2 * m2 + C1, B2 = (e11 - m1 * m1) + (e22 - m2 * m2) + C2;
-    const float iB1 = 1.f / B1, iB2 = 1.f / B2, iB = iB1 * iB2;
-    const float S = A1 * A2 * iB;
+    // S = R1 R2 from the two ratios, each the product with the reciprocal plus one residual step, so
+    // that A == B gives exactly 1.  Where the image equals the target (m1 == m2, e11 == e22 == e12,
+    // hence A1 == B1 and A2 == B2 bit for bit) S is then exactly 1, dS/dm1 exactly 0 and
+    // dS/dE[xy] == -2 dS/dE[x^2], which the backward's window keeps: a converged pixel gets a
+    // gradient of exactly 0, not rounding noise of the size of 1/B2.
+    const float iB1 = 1.f / B1, iB2 = 1.f / B2;
+    const float q1 = A1 * iB1, q2 = A2 * iB2;
+    const float R1 = __builtin_fmaf(__builtin_fmaf(-B1, q1, A1), iB1, q1);
+    const float R2 = __builtin_fmaf(__builtin_fmaf(-B2, q2, A2), iB2, q2);
+    const float S = R1 * R2, t = R1 * iB2;
     const int py = y0 + 4 * j + i;
     if (px < W && py < H) {
       const size_t o = plane * HW + (size_t)py * W + px;
-      dmaps[o] = 2.f * m2 * (A2 - A1) * iB - 2.f * m1 * S * (iB1 - iB2);  // dS/dm1
-      dmaps[PHW + o] = -S * iB2;                                          // dS/dE[x^2]
-      dmaps[2 * PHW + o] = 2.f * A1 * iB;                                 // dS/dE[xy]
+      // dS/dm1 = R2 dR1/dm1 + R1 dR2/dm1, dR1/dm1 = 2 (m2 - m1 R1) / B1, dR2/dm1 = 2 (m1 R2 - m2) / B2
+      dmaps[o] = 2.f * (iB1 * R2 * (m2 - m1 * R1) + t * (m1 * R2 - m2));
+      dmaps[PHW + o] = -t * R2;     // dS/dE[x^2] = -S / B2
+      dmaps[2 * PHW + o] = 2.f * t;  // dS/dE[xy] = 2 A1 / (B1 B2)
       v += S;
     }
   }

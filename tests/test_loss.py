@@ -4,7 +4,14 @@ restatement oracle/ssim_oracle.py.
 
 Tolerances: the oracle is float64 and pinned to the reference's float32 outputs at 2e-6 (value)
 and 1e-5 relative + 1e-5 x max (gradient); the HIP kernels compute in float32 with a separable
-window, checked against the oracle at 2e-6 (value) and 1e-5 relative + 1e-5 x max (gradient)."""
+window, checked against the oracle at 2e-6 (value) and 1e-5 relative + 1e-5 x max (gradient).
+Those figures hold on the high-variance content used here (rand against rand + 0.1 noise, windowed
+variances about 0.08).  On smooth, near-converged content E[x^2] - m^2, A2 - A1 and 1/B1 - 1/B2 cancel
+in float32 and the reference's own float32 formulation misses them by a factor of 30 and more (up to
+7e-3 x max in the gradient, 3.4e-4 in the value); there the contract is the conditioning rule of
+tests/test_gpu_loss.py, max|hip - f64| <= 4 max|ref f32 - f64| + 1e-5 max|f64|, of which the kernels
+use at most 0.37 (gradient) and 0.21 (value) on MI355X, and an exactly 0 gradient where the image
+equals the target."""
 import numpy as np
 import pytest
 import torch
@@ -147,3 +154,91 @@ def test_gpu_photometric_loss_matches_separate_terms(device):
     assert abs(loss1.item() - loss2.item()) <= 1e-6 * abs(loss1.item())
     assert abs(Ll1.item() - Ll2.item()) <= 1e-6 * abs(Ll1.item())
     _close(a2.grad.cpu().numpy(), a1.grad.cpu().numpy(), rtol=1e-5, frac=1e-6, name="grad")
+
+
+def test_partial_count():
+    from diff_gaussian_rasterization import _native
+
+    lib = _native.load()
+    assert lib.gs_ssim_partial_count(1, 32, 32) == 1
+    assert lib.gs_ssim_partial_count(1, 33, 32) == 2
+    assert lib.gs_ssim_partial_count(3, 1080, 1920) == 6120
+
+
+def test_loss_abi_validation_without_gpu():
+    """The argument checks of the four C entries; placeholder pointers, every call returns before a launch."""
+    import ctypes
+
+    from diff_gaussian_rasterization import _native
+
+    lib = _native.load()
+    fake = [ctypes.c_void_p(0x10000 * (k + 1)) for k in range(6)]
+    win = ctypes.cast((ctypes.c_float * 11)(*[1.0 / 11] * 11), ctypes.c_void_p)
+
+    def calls(planes, H, W, ptrs):
+        w, a, b, c, d, e = ptrs
+        return {"ssim": lambda: lib.gs_ssim_forward(planes, H, W, w, a, b, c, d, e, None),
+                "photometric loss": lambda: lib.gs_photometric_loss_forward(planes, H, W, w, a, b, 0.2, c, d, e, None),
+                "photometric loss ": lambda: lib.gs_photometric_loss_backward(planes, H, W, w, a, b, c, 0.2, d, e, None)}
+
+    every = [win] + fake[:5]
+    for shape in ((0, 8, 8), (2, 0, 8), (2, 8, 0), (-1, 8, 8), (2, -3, 8), (2, 8, -3)):
+        for name, call in calls(*shape, every).items():
+            assert call() != 0, (name, shape)
+            assert _native.last_error() == f"{name.strip()}: empty image", (name, shape)
+    for k in range(6):
+        ptrs = list(every)
+        ptrs[k] = None
+        for name, call in calls(2, 8, 8, ptrs).items():
+            assert call() != 0, (name, k)
+            assert _native.last_error() == f"{name.strip()}: missing pointer", (name, k)
+
+    def backward(planes, channels, H, W, ptrs=every):
+        return lib.gs_ssim_backward(planes, channels, H, W, *ptrs, None)
+
+    for bad in ((6, 0, 8, 8), (6, -3, 8, 8), (6, 4, 8, 8), (2, 3, 8, 8), (0, 3, 8, 8), (6, 3, 0, 8), (6, 3, 8, 0),
+                (6, 3, -1, 8), (6, 3, 8, -1)):
+        assert backward(*bad) != 0, bad
+        assert _native.last_error() == "ssim: bad shape", bad
+    for k in range(6):
+        ptrs = list(every)
+        ptrs[k] = None
+        assert backward(6, 3, 8, 8, ptrs) != 0, k
+        assert _native.last_error() == "ssim: missing pointer", k
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_loss_ref_matches_oracle_and_golden(case):
+    """tests/loss_ref.py, the reference of tests/test_gpu_loss.py: in float64 it is ssim_oracle bit for
+    bit, in float32 (the reference project's own arithmetic) it meets the goldens' tolerance."""
+    import loss_ref
+
+    a0, b0 = torch.tensor(G[f"{case}_img1"]), torch.tensor(G[f"{case}_img2"])
+    a = a0.double().requires_grad_(True)  # a float64 leaf: the oracle's gradient unrounded
+    s = ssim_oracle.ssim(a, b0)
+    s.backward()
+    loss, l1, val, smap, grad = loss_ref.reference(a0, b0, None, torch.float64)
+    assert smap.shape == a0.shape and grad.dtype == torch.float64
+    assert val.item() == s.item() and loss.item() == s.item() and torch.equal(grad, a.grad)
+    assert l1.item() == ssim_oracle.l1_loss(a0, b0).item()
+    assert smap.mean().item() == s.item()
+    want_loss, want_l1, want_grad = _oracle_photometric(a0.double(), b0, 0.2)
+    loss, l1, _, _, grad = loss_ref.reference(a0, b0, 0.2, torch.float64)
+    assert loss.item() == want_loss and l1.item() == want_l1 and np.array_equal(grad.numpy(), want_grad)
+    if a0.dim() == 4:
+        w = [1.0, -2.5, 0.25][:a0.shape[0]]
+        a3 = a0.double().requires_grad_(True)
+        s3 = ssim_oracle.ssim(a3, b0, size_average=False)
+        (s3 * torch.tensor(w, dtype=torch.float64)).sum().backward()
+        _, _, vals, _, grad = loss_ref.reference(a0, b0, None, torch.float64, weights=w)
+        assert torch.equal(vals, s3.detach()) and torch.equal(grad, a3.grad)
+    loss, l1, val, smap, grad = loss_ref.reference(a0, b0, None, torch.float32)
+    assert grad.dtype == torch.float32 and smap.dtype == torch.float32
+    assert abs(val.item() - float(G[f"{case}_ssim"])) < 2e-6
+    _close(grad.numpy(), G[f"{case}_grad"], name="float32 grad")
+    assert abs(l1.item() - float(G[f"{case}_l1"])) < 1e-6
+    if f"{case}_ssim_per_image" in G.files:
+        B = a0.shape[0]
+        _, _, vals, _, grad = loss_ref.reference(a0, b0, None, torch.float32, weights=[1.0] * B)
+        np.testing.assert_allclose(vals.numpy(), G[f"{case}_ssim_per_image"], atol=2e-6)
+        _close(grad.numpy(), G[f"{case}_grad_per_image_sum"], name="float32 grad per image")
