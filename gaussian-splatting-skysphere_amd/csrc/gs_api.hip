@@ -1567,7 +1567,30 @@ int gs_sky_compose_backward(int W, int H, const float* viewmatrix, float tanfovx
   if (dL_dtexture && (((uintptr_t)scratch) & 15)) return set_error("sky: scratch must be 16-byte aligned"), 1;
   if (!dL_dalpha && !dL_dtexture) return 0;
   sky_backward(W, H, viewmatrix, tanfovx, tanfovy, Hs, Ws, texture, alpha, dL_dimage, dL_dalpha, dL_dtexture,
-               accumulate_texture != 0, (char*)scratch, (hipStream_t)stream);
+               accumulate_texture != 0, (char*)scratch, nullptr, false, nullptr, (hipStream_t)stream);
+  return t_failed ? 1 : 0;
+}
+
+/* GSRAST_HAS_SKY_CAMERA */
+size_t gs_sky_camera_scratch_bytes(int W, int H) { return W > 0 && H > 0 ? sky_camera_scratch_bytes(W, H) : 0; }
+
+int gs_sky_compose_backward_camera(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
+                                   const float* texture, const float* alpha, const float* dL_dimage, float* dL_dalpha,
+                                   float* dL_dtexture, int accumulate_texture, void* scratch, float* dL_dviewmatrix,
+                                   int accumulate_view, void* camera_scratch, void* stream) {
+  clear_error(0);
+  if (!sky_shape_ok(W, H, Hs, Ws)) return 1;
+  if (!viewmatrix || !texture || !dL_dimage) return set_error("sky: missing pointer"), 1;
+  if (dL_dtexture && !scratch) return set_error("sky: dL_dtexture needs the scratch of gs_sky_scratch_bytes"), 1;
+  if (dL_dtexture && (((uintptr_t)scratch) & 15)) return set_error("sky: scratch must be 16-byte aligned"), 1;
+  if (dL_dviewmatrix && !camera_scratch)
+    return set_error("sky: dL_dviewmatrix needs the scratch of gs_sky_camera_scratch_bytes"), 1;
+  if (dL_dviewmatrix && (((uintptr_t)camera_scratch) & 15))
+    return set_error("sky: camera_scratch must be 16-byte aligned"), 1;
+  if (!dL_dalpha && !dL_dtexture && !dL_dviewmatrix) return 0;
+  sky_backward(W, H, viewmatrix, tanfovx, tanfovy, Hs, Ws, texture, alpha, dL_dimage, dL_dalpha, dL_dtexture,
+               accumulate_texture != 0, (char*)scratch, dL_dviewmatrix, accumulate_view != 0, (double*)camera_scratch,
+               (hipStream_t)stream);
   return t_failed ? 1 : 0;
 }
 

@@ -581,9 +581,13 @@ constexpr int SKY_MAX_TEX = 1 << 24;  // texture rows / columns: texel indices s
 size_t sky_scratch_bytes(int Hs, int Ws);
 void sky_forward(int W, int H, const float* view, float tanfovx, float tanfovy, int Hs, int Ws, const float* tex,
                  const float* color, const float* alpha, float* out, hipStream_t st);
+// dview != null (gs_sky_compose_backward_camera): the pass also sums dL/dviewmatrix, nine fp64 sums and a
+// zero (whole 16-B pairs) per 16 x 16 block in cam_scratch, then one finishing workgroup
+constexpr int SKY_CAM_ROW = 10, SKY_CAM_FINISH_THREADS = 1024;
+size_t sky_camera_scratch_bytes(int W, int H);
 void sky_backward(int W, int H, const float* view, float tanfovx, float tanfovy, int Hs, int Ws, const float* tex,
                   const float* alpha, const float* dimage, float* dalpha, float* dtex, bool accumulate, char* scratch,
-                  hipStream_t st);
+                  float* dview, bool accumulate_view, double* cam_scratch, hipStream_t st);
 constexpr int ADAM_MAX_TENSORS = 16;  // parameter tensors per Adam launch
 // ---- Adam (torch.optim.Adam semantics), shared by k_adam and the fused per-Gaussian backward ----
 struct AdamConsts {

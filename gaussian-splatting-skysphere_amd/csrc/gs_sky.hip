@@ -30,6 +30,21 @@
 // one global atomic per touched texel and channel.  A block whose box exceeds SKY_BOX texels -- a block
 // on the atan2 seam (its unwrapped columns span the texture), next to a pole, or a texture much finer
 // than the image -- adds its twelve contributions per pixel straight to global memory.
+//
+// dL/dviewmatrix (k_sky_bwd<true>, gs_sky_compose_backward_camera) rides on the same pass.  With
+// gm_c = g_c (1 - alpha), rho^2 = d.x^2 + d.z^2, l^2 = rho^2 + d.y^2 and the sample's two slopes
+//   a = sum_c gm_c [(t01 - t00) + fy ((t11 - t10) - (t01 - t00))]   (along fx)
+//   b = sum_c gm_c (bot - top)                                      (along fy; 0 where the rows clamp to one)
+// the ray's gradient is
+//   dL/dd.x =  a (Ws / 2pi) d.z / rho^2 - b (Hs / pi) d.y d.x / (rho l^2)
+//   dL/dd.z = -a (Ws / 2pi) d.x / rho^2 - b (Hs / pi) d.y d.z / (rho l^2)
+//   dL/dd.y =  b (Hs / pi) rho / l^2
+// and dL/dV[i][j] = sum over pixels of dL/dd_i d_cam_j (i, j < 3; floor carries no gradient, the sky at
+// infinity does not see row 3 or column 3).  A pixel contributes exactly 0 when 1 - alpha == 0, when
+// a == 0 and b == 0, when rho^2 == 0 or when one of its nine terms is not finite (the exact pole, a
+// degenerate matrix, a non-finite g).  The nine fp32 terms of a block's pixels are summed in fp64 in a
+// fixed order (through LDS, as k_camera_grad does) into one row of the scratch, and k_sky_cam_finish,
+// one workgroup, adds the rows in index order: no float atomics, the same bits on every run.
 #include <limits.h>
 
 #include "gs_internal.h"
@@ -50,15 +65,21 @@ struct SkyTap {
   float fx, fy;
 };
 
+struct SkyRay {
+  float cx, cy;      // d_cam = (cx, cy, 1)
+  float dx, dy, dz;  // the world ray, not normalised
+};
+
 // Every index is forced into range whatever the ray (a degenerate view matrix gives NaN: fmaxf
 // drops it), so a tap never addresses outside the texture.
 __device__ __forceinline__ SkyTap sky_tap(const float* __restrict__ view, float tanfovx, float tanfovy, int W, int H,
-                                          int Hs, int Ws, int x, int y) {
+                                          int Hs, int Ws, int x, int y, SkyRay* ray = nullptr) {
   const float cx = ((float)(2 * x + 1) / (float)W - 1.0f) * tanfovx;
   const float cy = ((float)(2 * y + 1) / (float)H - 1.0f) * tanfovy;
   const float dx = view[0] * cx + view[1] * cy + view[2];
   const float dy = view[4] * cx + view[5] * cy + view[6];
   const float dz = view[8] * cx + view[9] * cy + view[10];
+  if (ray) *ray = SkyRay{cx, cy, dx, dy, dz};
   const float len = sqrtf(dx * dx + dy * dy + dz * dz);
   const float u = atan2f(dx, dz) / 6.28318530717958647692f + 0.5f;
   const float v = acosf(fminf(fmaxf(-dy / len, -1.0f), 1.0f)) / 3.14159265358979323846f;
@@ -141,15 +162,56 @@ __device__ __forceinline__ unsigned long long sky_fixed(float c, double lim, dou
   return (unsigned long long)(long long)__builtin_rint(v);
 }
 
+__device__ __forceinline__ bool sky_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }  // false for NaN
+
+// The pixel's nine terms of dL/dV (header comment), v[3 i + j] = dL/dd_i d_cam_j, all zero under the
+// zero rules.  gc: the pixel's g, om: 1 - alpha.
+__device__ __forceinline__ void sky_view_terms(const float* __restrict__ tex, size_t TS, const SkyTap& t,
+                                               const SkyRay& r, int Hs, int Ws, const float gc[3], float om,
+                                               float v[9]) {
+  float sa[3], sb[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const float* ra = tex + c * TS + (size_t)t.ya * Ws;
+    const float* rb = tex + c * TS + (size_t)t.yb * Ws;
+    const float t00 = ra[t.xa], t01 = ra[t.xb], t10 = rb[t.xa], t11 = rb[t.xb];
+    const float top = t00 + t.fx * (t01 - t00);
+    const float bot = t10 + t.fx * (t11 - t10);
+    sa[c] = (t01 - t00) + t.fy * ((t11 - t10) - (t01 - t00));
+    sb[c] = bot - top;  // ya == yb: the same operations on the same texels, exactly 0
+  }
+  const float gm[3] = {gc[0] * om, gc[1] * om, gc[2] * om};
+  const float a = (gm[0] * sa[0] + gm[1] * sa[1]) + gm[2] * sa[2];
+  const float b = (gm[0] * sb[0] + gm[1] * sb[1]) + gm[2] * sb[2];
+  const float rho2 = r.dx * r.dx + r.dz * r.dz, l2 = rho2 + r.dy * r.dy, rho = sqrtf(rho2);
+  const float ak = a * ((float)Ws / 6.28318530717958647692f), bk = b * ((float)Hs / 3.14159265358979323846f);
+  const float A = ak / rho2, B = bk / (rho * l2);
+  const float gd[3] = {A * r.dz - (B * r.dy) * r.dx, bk * rho / l2, -(A * r.dx) - (B * r.dy) * r.dz};
+  bool ok = om != 0.0f && (a != 0.0f || b != 0.0f) && rho2 != 0.0f;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    v[3 * i] = gd[i] * r.cx;
+    v[3 * i + 1] = gd[i] * r.cy;
+    v[3 * i + 2] = gd[i];
+    ok = ok && sky_finite(v[3 * i]) && sky_finite(v[3 * i + 1]) && sky_finite(v[3 * i + 2]);
+  }
+  if (!ok)
+#pragma unroll
+    for (int k = 0; k < 9; k++) v[k] = 0.0f;
+}
+
 // dalpha == nullptr / acc == nullptr: that gradient is not produced.  maxbits: the word k_sky_absmax
-// left; acc: [3, Hs, Ws] fixed-point sums (zeroed by k_sky_clear).
+// left; acc: [3, Hs, Ws] fixed-point sums (zeroed by k_sky_clear).  CAM: the block's nine sums of
+// dL/dviewmatrix go to row blockIdx.y gridDim.x + blockIdx.x of cam_partial (SKY_CAM_ROW doubles).
+template <bool CAM>
 __global__ __launch_bounds__(SKY_T* SKY_T) void k_sky_bwd(int W, int H, const float* __restrict__ view, float tanfovx,
                                                           float tanfovy, int Hs, int Ws,
                                                           const float* __restrict__ tex,
                                                           const float* __restrict__ alpha,
                                                           const float* __restrict__ g, float* __restrict__ dalpha,
                                                           const uint32_t* __restrict__ maxbits, int log_hw,
-                                                          unsigned long long* __restrict__ acc) {
+                                                          unsigned long long* __restrict__ acc,
+                                                          double* __restrict__ cam_partial) {
   __shared__ int s_box[4][4];  // per wave: min / max unwrapped column, min / max row
   __shared__ unsigned long long s_acc[3][SKY_BOX];
   const int tid = threadIdx.x;
@@ -158,9 +220,10 @@ __global__ __launch_bounds__(SKY_T* SKY_T) void k_sky_bwd(int W, int H, const fl
   const bool inside = x < W && y < H;
   const size_t HW = (size_t)H * W, p = (size_t)y * W + x, TS = (size_t)Hs * Ws;
   SkyTap t = {};
+  SkyRay ray = {};
   float gc[3] = {0.0f, 0.0f, 0.0f}, om = 0.0f;
   if (inside) {
-    t = sky_tap(view, tanfovx, tanfovy, W, H, Hs, Ws, x, y);
+    t = sky_tap(view, tanfovx, tanfovy, W, H, Hs, Ws, x, y, CAM ? &ray : nullptr);
 #pragma unroll
     for (int c = 0; c < 3; c++) gc[c] = g[c * HW + p];
     om = 1.0f - (alpha ? alpha[p] : 0.0f);
@@ -169,6 +232,33 @@ __global__ __launch_bounds__(SKY_T* SKY_T) void k_sky_bwd(int W, int H, const fl
 #pragma unroll
       for (int c = 0; c < 3; c++) s[c] = sky_sample(tex + c * TS, t, Ws);
       dalpha[p] = -((gc[0] * s[0] + gc[1] * s[1]) + gc[2] * s[2]);
+    }
+  }
+  if constexpr (CAM) {
+    // the block's nine sums, k_camera_grad's order: thread (k, s) adds the terms k of pixels s, s + 8,
+    // ... in fp64, then the eight partial sums in order.  Lanes outside the image hold zeros.
+    constexpr int STRIDE = SKY_T * SKY_T + 8;
+    __shared__ float s_v[9][STRIDE];
+    __shared__ double s_p[9][8];
+    float v[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (inside) sky_view_terms(tex, TS, t, ray, Hs, Ws, gc, om, v);
+#pragma unroll
+    for (int k = 0; k < 9; k++) s_v[k][tid] = v[k];
+    lds_barrier();
+    if (tid < 9 * 8) {
+      const float* col = &s_v[tid >> 3][tid & 7];
+      double sum = 0.0;
+#pragma unroll
+      for (int k = 0; k < SKY_T * SKY_T / 8; k++) sum = sum + (double)col[8 * k];
+      s_p[tid >> 3][tid & 7] = sum;
+    }
+    lds_barrier();
+    if (tid < SKY_CAM_ROW) {
+      double sum = 0.0;
+      if (tid < 9)
+#pragma unroll
+        for (int s = 0; s < 8; s++) sum = sum + s_p[tid][s];
+      cam_partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SKY_CAM_ROW + tid] = sum;
     }
   }
   if (!acc) return;  // uniform
@@ -245,6 +335,46 @@ __global__ __launch_bounds__(256) void k_sky_finish(size_t n, const long long* _
   }
 }
 
+// One workgroup: the nb rows of k_sky_bwd<true> summed in fp64 in a fixed order (k_camera_grad_finish's
+// form: GROUPS row groups of SKY_CAM_ROW / 2 column pairs, each thread over its rows rg, rg + GROUPS,
+// ... with whole 16-B loads, then the groups in order), and the 16 floats of dL/dviewmatrix written or
+// added (fp32 old + new), row 3 and column 3 as zeros.  8,160 rows (638 KB) at 1080p.
+__global__ __launch_bounds__(SKY_CAM_FINISH_THREADS) void k_sky_cam_finish(const double* __restrict__ partial, long long nb,
+                                                                           int accumulate, float* __restrict__ dview) {
+  constexpr int PAIRS = SKY_CAM_ROW / 2, GROUPS = SKY_CAM_FINISH_THREADS / PAIRS;
+  __shared__ double s_grp[GROUPS][SKY_CAM_ROW];
+  __shared__ double s_fin[SKY_CAM_ROW];
+  const int t = (int)threadIdx.x;
+  if (t < GROUPS * PAIRS) {
+    const int cp = t % PAIRS, rg = t / PAIRS;
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll 8
+    for (long long r = rg; r < nb; r += GROUPS) {
+      const double2 q = reinterpret_cast<const double2*>(partial)[(size_t)r * PAIRS + cp];
+      a0 = a0 + q.x;
+      a1 = a1 + q.y;
+    }
+    s_grp[rg][2 * cp] = a0;
+    s_grp[rg][2 * cp + 1] = a1;
+  }
+  lds_barrier();
+  if (t < SKY_CAM_ROW) {
+    double a = 0.0;
+    for (int rg = 0; rg < GROUPS; rg++) a = a + s_grp[rg][t];
+    s_fin[t] = a;
+  }
+  lds_barrier();
+  if (t < 16) {
+    const float v = (t >> 2) < 3 && (t & 3) < 3 ? (float)s_fin[3 * (t >> 2) + (t & 3)] : 0.0f;
+    dview[t] = accumulate ? dview[t] + v : v;
+  }
+}
+
+// the view gradient's scratch: one row of SKY_CAM_ROW doubles per 16 x 16 block of the image
+size_t sky_camera_scratch_bytes(int W, int H) {
+  return (size_t)((W + SKY_T - 1) / SKY_T) * (size_t)((H + SKY_T - 1) / SKY_T) * SKY_CAM_ROW * sizeof(double);
+}
+
 // scratch: 16 bytes (the max word), then [3, Hs, Ws] 64-bit sums; a whole number of 16-byte units
 size_t sky_scratch_bytes(int Hs, int Ws) { return (16 + 3 * (size_t)Hs * (size_t)Ws * 8 + 15) & ~(size_t)15; }
 
@@ -262,7 +392,7 @@ void sky_forward(int W, int H, const float* view, float tanfovx, float tanfovy, 
 
 void sky_backward(int W, int H, const float* view, float tanfovx, float tanfovy, int Hs, int Ws, const float* tex,
                   const float* alpha, const float* dimage, float* dalpha, float* dtex, bool accumulate, char* scratch,
-                  hipStream_t st) {
+                  float* dview, bool accumulate_view, double* cam_scratch, hipStream_t st) {
   const dim3 grid((W + SKY_T - 1) / SKY_T, (H + SKY_T - 1) / SKY_T);
   uint32_t* maxbits = reinterpret_cast<uint32_t*>(scratch);
   unsigned long long* acc = dtex ? reinterpret_cast<unsigned long long*>(scratch + 16) : nullptr;
@@ -274,8 +404,15 @@ void sky_backward(int W, int H, const float* view, float tanfovx, float tanfovy,
     GS_LAUNCH("sky_clear", k_sky_clear, sky_stream_grid(n16), dim3(256), 0, st, reinterpret_cast<uint4*>(scratch), n16);
     GS_LAUNCH("sky_absmax", k_sky_absmax, sky_stream_grid(n_img / 4, SKY_MAX_BLOCKS), dim3(256), 0, st, dimage, n_img, maxbits);
   }
-  GS_LAUNCH("sky_bwd", k_sky_bwd, grid, dim3(SKY_T * SKY_T), 0, st, W, H, view, tanfovx, tanfovy, Hs, Ws, tex, alpha,
-            dimage, dalpha, maxbits, log_hw, acc);
+  if (dview)
+    GS_LAUNCH("sky_bwd_cam", k_sky_bwd<true>, grid, dim3(SKY_T * SKY_T), 0, st, W, H, view, tanfovx, tanfovy, Hs, Ws,
+              tex, alpha, dimage, dalpha, maxbits, log_hw, acc, cam_scratch);
+  else
+    GS_LAUNCH("sky_bwd", k_sky_bwd<false>, grid, dim3(SKY_T * SKY_T), 0, st, W, H, view, tanfovx, tanfovy, Hs, Ws,
+              tex, alpha, dimage, dalpha, maxbits, log_hw, acc, (double*)nullptr);
+  if (dview)
+    GS_LAUNCH("sky_cam_finish", k_sky_cam_finish, dim3(1), dim3(SKY_CAM_FINISH_THREADS), 0, st, cam_scratch,
+              (long long)grid.x * grid.y, accumulate_view ? 1 : 0, dview);
   if (dtex)
     GS_LAUNCH("sky_finish", k_sky_finish, sky_stream_grid(n_tex), dim3(256), 0, st, n_tex,
               reinterpret_cast<const long long*>(acc), maxbits, log_hw, accumulate ? 1 : 0, dtex);

@@ -178,6 +178,10 @@ SIGNATURES = {
     "gs_sky_compose_forward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gs_sky_compose_backward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i,
                                        _c_p, _c_p]),
+    # GSRAST_HAS_SKY_CAMERA: the sky's dL/dviewmatrix on the same pass
+    "gs_sky_camera_scratch_bytes": (_c_sz, [_c_i, _c_i]),
+    "gs_sky_compose_backward_camera": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                              _c_i, _c_p, _c_p, _c_i, _c_p, _c_p]),
     "gs_mark_visible": (_c_i, [_c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gs_knn_scratch_bytes": (_c_sz, [_c_i]),
     "gs_knn_mean_dist2": (_c_i, [_c_i, _c_p, _c_p, _c_p, _c_p]),

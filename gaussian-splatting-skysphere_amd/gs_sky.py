@@ -19,6 +19,12 @@ centres, the inverse of the rasterizer's projection -- turned into the world by
 Gradients flow to the texture, to alpha (and through the rasterizer's aux backward to the
 opacities and geometry) and to the colour.  dL/dtexture is bitwise reproducible (64-bit fixed-point
 sums).  `gs_train.FusedAdam` steps `sky.texture` like any other parameter.
+
+Pose refinement: with `camera_grads=True` a `settings.viewmatrix` that requires grad also receives
+the sky's dL/dviewmatrix [4, 4] (the rotation block; a sky at infinity does not see the translation),
+summed on the same backward pass in fp64 in a fixed order (gs_sky_compose_backward_camera, bitwise
+reproducible).  `render_with_sky(..., camera_grads=True)` hands the flag to the rasterizer too, and
+autograd adds the two shares; `gs_pose.CameraTwist` chains the camera tensors to a pose.
 """
 from __future__ import annotations
 
@@ -57,7 +63,8 @@ def _f32(t, name):
 
 class _Compose(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, color, alpha, texture, settings):
+    def forward(ctx, color, alpha, texture, settings, viewmatrix):
+        # (viewmatrix: settings.viewmatrix itself, an input for the graph's sake -- camera_grads)
         if not texture.is_cuda or (color is not None and not color.is_cuda) or (alpha is not None and not alpha.is_cuda):
             raise RuntimeError("gs_sky.compose (MI355X/HIP) needs device tensors; there is no CPU path")
         H, W = int(settings.image_height), int(settings.image_width)
@@ -95,13 +102,25 @@ class _Compose(torch.autograd.Function):
         tex, alp, view = ctx.saved_tensors
         W, H, Hs, Ws, tfx, tfy, alpha_shape = ctx.geom
         need_color, need_alpha, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_view = ctx.needs_input_grad[4]
         if grad is None:
-            return None, None, None, None
+            return None, None, None, None, None
         dev = tex.device
         g = grad.to(torch.float32).contiguous()
         dalpha = torch.empty((H, W), dtype=torch.float32, device=dev) if need_alpha else None
         dtex = torch.empty_like(tex) if need_tex else None
-        if need_alpha or need_tex:
+        dview = None
+        if need_view:
+            dview = torch.empty((4, 4), dtype=torch.float32, device=dev)
+            scratch = (torch.empty((_lib.gs_sky_scratch_bytes(Hs, Ws),), dtype=torch.uint8, device=dev)
+                       if need_tex else None)
+            cam_scratch = torch.empty((_lib.gs_sky_camera_scratch_bytes(W, H),), dtype=torch.uint8, device=dev)
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            with torch.cuda.device(dev):
+                _native.check(_lib.gs_sky_compose_backward_camera(
+                    W, H, _p(view), tfx, tfy, Hs, Ws, _p(tex), _p(alp), _p(g), _p(dalpha), _p(dtex), 0, _p(scratch),
+                    _p(dview), 0, _p(cam_scratch), st), "sky backward")
+        elif need_alpha or need_tex:
             scratch = (torch.empty((_lib.gs_sky_scratch_bytes(Hs, Ws),), dtype=torch.uint8, device=dev)
                        if need_tex else None)
             st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -110,16 +129,27 @@ class _Compose(torch.autograd.Function):
                                                            _p(dalpha), _p(dtex), 0, _p(scratch), st), "sky backward")
         if dalpha is not None:
             dalpha = dalpha.view(alpha_shape)
-        return (g if need_color else None), dalpha, dtex, None
+        return (g if need_color else None), dalpha, dtex, None, dview
 
 
-def compose(color, alpha, texture, settings):
+def compose(color, alpha, texture, settings, camera_grads=False):
     """image [3, H, W] = color + (1 - alpha) * sky(texture) for the camera of `settings`
     (a GaussianRasterizationSettings: image size, tanfovx / tanfovy, viewmatrix).
 
     color [3, H, W] or None (0), alpha [H, W] / [1, H, W] or None (0), texture [3, Hs, Ws]; fp32
-    device tensors.  Differentiable w.r.t. all three (dL/dcolor is the incoming gradient itself)."""
-    return _Compose.apply(color, alpha, texture, settings)
+    device tensors.  Differentiable w.r.t. all three (dL/dcolor is the incoming gradient itself).
+
+    camera_grads: a settings.viewmatrix that requires grad (a leaf or not; float32 [4, 4] on the
+    texture's device) receives the sky's dL/dviewmatrix as well, row 3 and column 3 zero.  Without it,
+    or with a matrix that does not require grad, the matrix is a constant: the call as it always was.
+    tanfovx, tanfovy, projmatrix and campos get nothing from the sky."""
+    V = settings.viewmatrix
+    if camera_grads and isinstance(V, torch.Tensor) and V.requires_grad:
+        if V.dtype != torch.float32 or tuple(V.shape) != (4, 4) or V.device != texture.device:
+            raise ValueError("gs_sky.compose: camera_grads needs settings.viewmatrix as a float32 [4, 4] tensor on "
+                             f"the texture's device (got {V.dtype} {tuple(V.shape)} on {V.device})")
+        return _Compose.apply(color, alpha, texture, settings, V)
+    return _Compose.apply(color, alpha, texture, settings, None)
 
 
 class SkySphere(torch.nn.Module):
@@ -132,21 +162,28 @@ class SkySphere(torch.nn.Module):
             raise ValueError(f"SkySphere: texture size must be positive (got {Hs} x {Ws})")
         self.texture = torch.nn.Parameter(torch.full((3, int(Hs), int(Ws)), float(init), dtype=torch.float32))
 
-    def forward(self, color, alpha, settings):
-        return compose(color, alpha, self.texture, settings)
+    def forward(self, color, alpha, settings, camera_grads=False):
+        return compose(color, alpha, self.texture, settings, camera_grads)
 
-    def render(self, settings):
+    def render(self, settings, camera_grads=False):
         """The bare sky of the camera, [3, H, W] (no splats: colour 0, alpha 0)."""
-        return compose(None, None, self.texture, settings)
+        return compose(None, None, self.texture, settings, camera_grads)
 
 
-def render_with_sky(rasterizer, sky, **inputs):
+def render_with_sky(rasterizer, sky, camera_grads=False, **inputs):
     """One render with the sky behind the splats: calls `rasterizer(**inputs, aux_outputs=True)` and
     composes its colour and alpha with `sky` (a SkySphere).  Returns (image, radii, invdepth, alpha).
     The rasterizer's own background must be zero: it is already part of `color`, and a non-zero one
-    would be added on top of the sky."""
+    would be added on top of the sky.
+
+    camera_grads=True goes to both calls: the camera tensors of the settings that require grad get the
+    rasterizer's gradients, and the view matrix the sky's share on top (autograd adds the two).  The
+    rasterizer's refusals (prepared views, split SH rows, deferring gradient owners) are its own."""
     s = rasterizer.raster_settings
     if bool((s.bg != 0).any()):
         raise ValueError("render_with_sky: settings.bg must be all zeros (the sky is the background)")
-    color, radii, invdepth, alpha = rasterizer(**inputs, aux_outputs=True)
-    return sky(color, alpha, s), radii, invdepth, alpha
+    if not camera_grads:
+        color, radii, invdepth, alpha = rasterizer(**inputs, aux_outputs=True)
+        return sky(color, alpha, s), radii, invdepth, alpha
+    color, radii, invdepth, alpha = rasterizer(**inputs, aux_outputs=True, camera_grads=True)
+    return sky(color, alpha, s, camera_grads=True), radii, invdepth, alpha

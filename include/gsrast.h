@@ -69,6 +69,10 @@ extern "C" {
  * gs_sky_compose_backward. */
 #define GSRAST_HAS_SKY 1
 
+/* The skysphere's view-matrix gradient (additive, same ABI version): gs_sky_camera_scratch_bytes,
+ * gs_sky_compose_backward_camera. */
+#define GSRAST_HAS_SKY_CAMERA 1
+
 /* Camera gradients (additive, same ABI version): gs_camera_grad_scratch_bytes, gs_backward_camera. */
 #define GSRAST_HAS_CAMERA_GRAD 1
 
@@ -545,6 +549,35 @@ int gs_sky_compose_forward(int W, int H, const float* viewmatrix, float tanfovx,
 int gs_sky_compose_backward(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
                             const float* texture, const float* alpha, const float* dL_dimage, float* dL_dalpha,
                             float* dL_dtexture, int accumulate_texture, void* scratch, void* stream);
+
+/* ---- the skysphere's view-matrix gradient (GSRAST_HAS_SKY_CAMERA) ----
+ * gs_sky_compose_backward with one more output: dL_dviewmatrix[16], the row-major [4, 4] gradient of
+ * the viewmatrix argument through the rays d_i = sum_j V[i][j] d_cam_j (the same row-vector
+ * convention; the matrix is an independent input, the caller chains it to a pose).  With
+ * gm_c = g_c (1 - alpha), rho^2 = d.x^2 + d.z^2, l^2 = rho^2 + d.y^2, a = sum_c gm_c [(t01 - t00) +
+ * fy ((t11 - t10) - (t01 - t00))] (the sample's slope along fx) and b = sum_c gm_c (bot - top) (along
+ * fy; 0 where the two rows clamp to one):
+ *   dL/dd.x =  a (Ws / 2pi) d.z / rho^2 - b (Hs / pi) d.y d.x / (rho l^2)
+ *   dL/dd.z = -a (Ws / 2pi) d.x / rho^2 - b (Hs / pi) d.y d.z / (rho l^2)
+ *   dL/dd.y =  b (Hs / pi) rho / l^2
+ *   dL_dviewmatrix[4 i + j] = sum over pixels of dL/dd_i d_cam_j   (i, j < 3)
+ * floor carries no gradient.  Row 3 and column 3 are structural zeros (a sky at infinity does not see
+ * the translation), written as such.  A pixel contributes exactly zero when 1 - alpha == 0, when
+ * a == 0 and b == 0, and when rho^2 == 0 or one of its terms is not finite (the exact pole, a
+ * degenerate matrix).  tanfovx / tanfovy get no gradient.
+ * The sums are fp64 in a fixed order without float atomics (a row of doubles per 16 x 16 pixel block
+ * in camera_scratch, one finishing workgroup over the rows in index order): bit-identical from run to
+ * run.  The 16 floats are written (accumulate_view 0) or added as fp32 old + new (1).
+ * camera_scratch holds gs_sky_camera_scratch_bytes(W, H) bytes (0 for a non-positive size; a multiple
+ * of 16), 16-byte aligned, needed only with dL_dviewmatrix.  dL_dviewmatrix == NULL: the call is
+ * gs_sky_compose_backward (same checks, launches and bits).  dL_dalpha and dL_dtexture may both be
+ * NULL: no texture scratch is needed then.  All argument checks fail on the host. */
+size_t gs_sky_camera_scratch_bytes(int W, int H);
+int gs_sky_compose_backward_camera(int W, int H, const float* viewmatrix, float tanfovx, float tanfovy, int Hs, int Ws,
+                                   const float* texture, const float* alpha, const float* dL_dimage, float* dL_dalpha,
+                                   float* dL_dtexture, int accumulate_texture, void* scratch,
+                                   float* dL_dviewmatrix /* [16] row-major, may be NULL */, int accumulate_view,
+                                   void* camera_scratch, void* stream);
 
 /* ---- fused Adam step  <-  torch.optim.Adam.step() of GaussianModel's optimizer
  *      (/root/reference/scene/gaussian_model.py:154-163, stepped at train.py:123-124) ----
