@@ -486,7 +486,46 @@ struct SrcTilesByRank {
     const uint32_t g = sorted_gid[s];
     return g < P ? tiles[g] : 0u;
   }
+  __device__ SrcTilesByRank view(uint64_t vstride) const {
+    return SrcTilesByRank{vptr(tiles, vstride), vptr(sorted_gid, vstride), P};
+  }
 };
+#if GS_VIEWS_SCAN_GATHER == 4
+// the batched K-view scan over the depth sort's packed values (id | min(count, PACK_MAX) <<
+// PACK_ID_BITS): a saturated count is looked up; the down sweep (CLEAN) leaves the plain id behind
+template <bool CLEAN>
+struct SrcPackedCounts {
+  const uint32_t* tiles;
+  uint32_t* sorted_gid;
+  uint32_t P;
+  __device__ uint32_t operator()(uint32_t s) const {
+    const uint32_t w = sorted_gid[s], g = w & PACK_ID_MASK, t = w >> PACK_ID_BITS;
+    if constexpr (CLEAN) sorted_gid[s] = g;
+    return t < PACK_MAX ? t : (g < P ? tiles[g] : 0u);
+  }
+  __device__ SrcPackedCounts view(uint64_t vstride) const {
+    return SrcPackedCounts{vptr(tiles, vstride), vptr(sorted_gid, vstride), P};
+  }
+};
+#endif
+#if GS_VIEWS_SCAN_GATHER == 2
+// the reduce sweep of the batched K-view scan: gathers like SrcTilesByRank and keeps the count at
+// its rank for the down sweep (SrcArray)
+struct SrcTilesByRankKeep {
+  const uint32_t *tiles, *sorted_gid;
+  uint32_t* by_rank;
+  uint32_t P;
+  __device__ uint32_t operator()(uint32_t s) const {
+    const uint32_t g = sorted_gid[s];
+    const uint32_t t = g < P ? tiles[g] : 0u;
+    by_rank[s] = t;
+    return t;
+  }
+  __device__ SrcTilesByRankKeep view(uint64_t vstride) const {
+    return SrcTilesByRankKeep{vptr(tiles, vstride), vptr(sorted_gid, vstride), vptr(by_rank, vstride), P};
+  }
+};
+#endif
 
 // instance offsets in depth order; also records, for every DUP_SLOTS-aligned slot, the depth rank
 // that owns it (the start of each load-balanced duplicate block)
@@ -500,6 +539,9 @@ struct DstOffsets {
     const uint32_t I = counters[CNT_NREND];
     if (!dup_balanced(I, P)) return;
     for (uint32_t m = (ex + DUP_SLOTS - 1) / DUP_SLOTS; m * DUP_SLOTS < ex + v && m * DUP_SLOTS < I; m++) first[m] = s;
+  }
+  __device__ DstOffsets view(uint64_t vstride) const {
+    return DstOffsets{vptr(offsets, vstride), vptr(first, vstride), vptr(counters, vstride), P};
   }
 };
 
@@ -595,9 +637,13 @@ void fwd_order(int P, const GeomPtrs& geo, hipStream_t st, uint32_t* host_counts
   // and drops the DEPTH_DROP ones (compaction), the later passes sort the V survivors; every
   // view's passes in one set of launches (blockIdx.y = view)
   if (lb_tiles(n) <= LB_STATIC_MAX) {
+    // (GS_VIEWS_SCAN_GATHER == 3, several views: the last pass also leaves tiles[gid] at the key's rank)
+    // (== 4: the first pass packs it beside the id, and the scan below unpacks it)
+    const bool ranked = GS_VIEWS_SCAN_GATHER >= 3 && views > 1;
     radix_sort_pairs(geo.keys_a, geo.vals_a, geo.keys_b, geo.vals_b, true, &geo.counters[CNT_V], n, 32,
                      geo.sort_scratch, st, /*drop_first=*/true, /*hist0_ready=*/true, nullptr, nullptr, nullptr,
-                     nullptr, GS_DEPTH_SORT_BLOCKS, views, vstride);
+                     nullptr, GS_DEPTH_SORT_BLOCKS, views, vstride, ranked ? geo.tiles : nullptr,
+                     ranked ? geo.rtiles_a : nullptr);
   } else {
     // larger scenes: the tile counts travel with the keys through the sort (read in index order by
     // the first pass), and the 3-launch scan reads them in depth order, coalesced (C5, 5M: the
@@ -606,11 +652,33 @@ void fwd_order(int P, const GeomPtrs& geo, hipStream_t st, uint32_t* host_counts
                      geo.sort_scratch, st, /*drop_first=*/true, /*hist0_ready=*/true, geo.tiles, geo.rtiles_a,
                      geo.rtiles_b, nullptr, GS_DEPTH_SORT_BLOCKS, views, vstride);
   }
-  for (int v = 0; v < views; v++) {
-    GeomPtrs g = geo;
-    if (v) geom_layout((size_t)P, &g, (char*)geo.splat + (uint64_t)v * vstride);
-    fwd_scan(P, g, st);
+  if (views == 1) {
+    fwd_scan(P, geo, st);
+    return;
   }
+  // several views: their offsets scans as one 3-launch scan (blockIdx.y = view; no workgroup waits
+  // for another, so this scan never sets ERR_LOOKBACK and leaves counters[CNT_LB_TILE] unused)
+  const DstOffsets dst{geo.offsets, geo.dup_first, geo.counters, n};
+  if (lb_tiles(n) > LB_STATIC_MAX) {  // the counts travelled with the keys
+    scan_exclusive(SrcArray{geo.tiles_by_rank}, dst, &geo.counters[CNT_V], n, geo.scan_partial, &geo.counters[CNT_I],
+                   st, views, vstride);
+    return;
+  }
+#if GS_VIEWS_SCAN_GATHER == 1
+  scan_exclusive(SrcTilesByRank{geo.tiles, geo.sorted_gid, n}, dst, &geo.counters[CNT_V], n, geo.scan_partial,
+                 &geo.counters[CNT_I], st, views, vstride);
+#elif GS_VIEWS_SCAN_GATHER == 2
+  scan_exclusive2(SrcTilesByRankKeep{geo.tiles, geo.sorted_gid, geo.rtiles_a, n}, SrcArray{geo.rtiles_a}, dst,
+                  &geo.counters[CNT_V], n, geo.scan_partial, &geo.counters[CNT_I], st, views, vstride);
+#elif GS_VIEWS_SCAN_GATHER == 4
+  scan_exclusive2(SrcPackedCounts<false>{geo.tiles, geo.sorted_gid, n}, SrcPackedCounts<true>{geo.tiles, geo.sorted_gid, n},
+                  dst, &geo.counters[CNT_V], n, geo.scan_partial, &geo.counters[CNT_I], st, views, vstride);
+#elif GS_VIEWS_SCAN_GATHER == 3
+  scan_exclusive(SrcArray{geo.rtiles_a}, dst, &geo.counters[CNT_V], n, geo.scan_partial, &geo.counters[CNT_I], st,
+                 views, vstride);
+#else
+#error "GS_VIEWS_SCAN_GATHER: 1, 2, 3 or 4"
+#endif
 }
 
 __global__ __launch_bounds__(64) void k_clear_flags(uint32_t* __restrict__ err, uint32_t bits) {

@@ -17,6 +17,22 @@
 
 namespace gs {
 
+// How the batched K-view offsets scan (gs_forward.hip fwd_order) gets each depth rank's tile count
+// tiles[sorted_gid[rank]]: 1 both sweeps gather it; 2 the reduce sweep gathers it and stores it in
+// rank order for the down sweep; 3 the depth sort's last scatter stores it in rank order for both
+// sweeps; 4 the depth sort's first pass, which reads the Gaussians in index order, packs
+// min(count, PACK_MAX) above the 20-bit id in the sort's value word, the counts travel through the
+// passes for free, both sweeps read them from the sorted values (a count >= PACK_MAX is looked up)
+// and the down sweep leaves the plain ids behind.  Only the chosen form is compiled (DESIGN.md §5
+// has the A/B).
+#ifndef GS_VIEWS_SCAN_GATHER
+#define GS_VIEWS_SCAN_GATHER 4
+#endif
+// form 4's value word: id in the low PACK_ID_BITS bits (up to 2^20 Gaussians: exactly the sizes of
+// the look-back ordering path, lb_tiles(P) <= LB_STATIC_MAX), min(count, PACK_MAX) above them
+constexpr int PACK_ID_BITS = 20;
+constexpr uint32_t PACK_ID_MASK = (1u << PACK_ID_BITS) - 1u, PACK_MAX = (1u << (32 - PACK_ID_BITS)) - 1u;
+
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 4;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // 1024 elements per tile
@@ -41,6 +57,18 @@ __device__ __forceinline__ uint32_t resolve_n(const uint32_t* n_dev, uint32_t n_
   if (n_dev == nullptr) return n_max;
   uint32_t n = *n_dev;
   return n < n_max ? n : n_max;
+}
+
+// View batching: one launch sorts or scans the same-shaped arrays of several views (blockIdx.y = view) whose
+// buffers lie `vstride` bytes apart (the views' geometry buffers are slices of one allocation).
+// vptr(p): this workgroup's view's copy of p (null stays null).
+template <class T>
+__device__ __forceinline__ T* vptr(T* p, uint64_t vstride) {
+  return p ? (T*)((char*)p + (uint64_t)blockIdx.y * vstride) : p;
+}
+template <class T>
+__device__ __forceinline__ const T* vptr(const T* p, uint64_t vstride) {
+  return p ? (const T*)((const char*)p + (uint64_t)blockIdx.y * vstride) : p;
 }
 
 // inclusive wave64 scan (u32)
@@ -68,10 +96,15 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sh, ui
   return before + inc - v;
 }
 
+// The three scan kernels take views like the radix kernels: blockIdx.y selects the view, and the
+// view's copy of every array (source, destination, n_dev, partial, total_out) lies blockIdx.y *
+// vstride bytes after view 0's; a functor's view(vstride) returns it with its pointers moved.
 template <class Src>
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(Src src, const uint32_t* n_dev, uint32_t n_max,
-                                                              uint32_t chunk, uint32_t* partial) {
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(Src src0, const uint32_t* n_dev, uint32_t n_max,
+                                                              uint32_t chunk, uint32_t* partial, uint64_t vstride) {
   __shared__ uint32_t sh[4];
+  const Src src = src0.view(vstride);
+  n_dev = vptr(n_dev, vstride), partial = vptr(partial, vstride);
   const uint32_t n = resolve_n(n_dev, n_max);
   const uint64_t start = (uint64_t)blockIdx.x * chunk;
   const uint64_t end = start + chunk < n ? start + chunk : n;
@@ -82,12 +115,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(Src src, const uin
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-// single workgroup (1024 lanes): exclusive scan of partial[0..nb) in place; total -> *total_out
+// single workgroup (1024 lanes) per view: exclusive scan of partial[0..nb) in place; total -> *total_out
 // (a template, like every kernel of this header: vague linkage, so the TUs that include it share one
 // exported kernel handle -- the launch log resolves it by name)
 template <int = 0>
-__global__ __launch_bounds__(1024) void k_scan_partials(uint32_t* partial, uint32_t nb, uint32_t* total_out) {
+__global__ __launch_bounds__(1024) void k_scan_partials(uint32_t* partial, uint32_t nb, uint32_t* total_out,
+                                                        uint64_t vstride) {
   __shared__ uint32_t sh[16];
+  partial = vptr(partial, vstride), total_out = vptr(total_out, vstride);
   const uint32_t lane = __lane_id(), wid = threadIdx.x >> 6;
   uint32_t carry = 0;
   for (uint32_t base = 0; base < nb; base += 1024) {
@@ -110,10 +145,13 @@ __global__ __launch_bounds__(1024) void k_scan_partials(uint32_t* partial, uint3
 }
 
 template <class Src, class Dst>
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_down(Src src, Dst dst, const uint32_t* n_dev,
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_down(Src src0, Dst dst0, const uint32_t* n_dev,
                                                             uint32_t n_max, uint32_t chunk,
-                                                            const uint32_t* partial) {
+                                                            const uint32_t* partial, uint64_t vstride) {
   __shared__ uint32_t sh[4];
+  const Src src = src0.view(vstride);
+  const Dst dst = dst0.view(vstride);
+  n_dev = vptr(n_dev, vstride), partial = vptr(partial, vstride);
   const uint32_t n = resolve_n(n_dev, n_max);
   const uint64_t start = (uint64_t)blockIdx.x * chunk;
   const uint64_t end = start + chunk < n ? start + chunk : n;
@@ -137,16 +175,22 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_down(Src src, Dst dst, co
   }
 }
 
-// host: run the 3-launch scan.  partial must hold >= plan.nb u32.
+// host: run the 3-launch scan.  partial must hold >= plan.nb u32.  views / vstride: `views` such
+// scans at once (the same three launches), view v's arrays lying v * vstride bytes after view 0's.
+template <class SrcUp, class Src, class Dst>
+inline void scan_exclusive2(SrcUp src_up, Src src, Dst dst, const uint32_t* n_dev, uint32_t n_max, uint32_t* partial,
+                            uint32_t* total_out, hipStream_t st, int views = 1, uint64_t vstride = 0) {
+  ScanPlan p = scan_plan(n_max);
+  GS_LAUNCH("scan_reduce", (k_scan_reduce<SrcUp>), dim3(p.nb, views), dim3(SCAN_THREADS), 0, st, src_up, n_dev, n_max,
+            p.chunk, partial, vstride);
+  GS_LAUNCH("scan_partials", k_scan_partials<>, dim3(1, views), dim3(1024), 0, st, partial, p.nb, total_out, vstride);
+  GS_LAUNCH("scan_down", (k_scan_down<Src, Dst>), dim3(p.nb, views), dim3(SCAN_THREADS), 0, st, src, dst, n_dev, n_max,
+            p.chunk, partial, vstride);
+}
 template <class Src, class Dst>
 inline void scan_exclusive(Src src, Dst dst, const uint32_t* n_dev, uint32_t n_max, uint32_t* partial,
-                           uint32_t* total_out, hipStream_t st) {
-  ScanPlan p = scan_plan(n_max);
-  GS_LAUNCH("scan_reduce", (k_scan_reduce<Src>), dim3(p.nb), dim3(SCAN_THREADS), 0, st, src, n_dev, n_max,
-            p.chunk, partial);
-  GS_LAUNCH("scan_partials", k_scan_partials<>, dim3(1), dim3(1024), 0, st, partial, p.nb, total_out);
-  GS_LAUNCH("scan_down", (k_scan_down<Src, Dst>), dim3(p.nb), dim3(SCAN_THREADS), 0, st, src, dst, n_dev, n_max,
-            p.chunk, partial);
+                           uint32_t* total_out, hipStream_t st, int views = 1, uint64_t vstride = 0) {
+  scan_exclusive2(src, src, dst, n_dev, n_max, partial, total_out, st, views, vstride);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -293,10 +337,12 @@ inline void scan_exclusive_lb(Src src, Dst dst, const uint32_t* n_dev, uint32_t 
 struct SrcArray {
   const uint32_t* a;
   __device__ uint32_t operator()(uint32_t i) const { return a[i]; }
+  __device__ SrcArray view(uint64_t vstride) const { return SrcArray{vptr(a, vstride)}; }
 };
 struct DstArray {
   uint32_t* a;
   __device__ void operator()(uint32_t i, uint32_t ex, uint32_t) const { a[i] = ex; }
+  __device__ DstArray view(uint64_t vstride) const { return DstArray{vptr(a, vstride)}; }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -357,18 +403,6 @@ inline size_t sort_scratch_words(uint64_t n_max) {
   if (tiles == 0) tiles = 1;
   const size_t nb = (size_t)(tiles < SORT_MAX_BLOCKS ? tiles : SORT_MAX_BLOCKS);
   return (size_t)RADIX * nb + RADIX + 16;
-}
-
-// View batching: one launch sorts the same-shaped arrays of several views (blockIdx.y = view) whose
-// buffers lie `vstride` bytes apart (the views' geometry buffers are slices of one allocation).
-// vptr(p): this workgroup's view's copy of p (null stays null).
-template <class T>
-__device__ __forceinline__ T* vptr(T* p, uint64_t vstride) {
-  return p ? (T*)((char*)p + (uint64_t)blockIdx.y * vstride) : p;
-}
-template <class T>
-__device__ __forceinline__ const T* vptr(const T* p, uint64_t vstride) {
-  return p ? (const T*)((const char*)p + (uint64_t)blockIdx.y * vstride) : p;
 }
 
 // lanes of this wave whose `bits`-bit digit equals mine (valid lanes only)
@@ -466,7 +500,11 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_rowscan(uint32_t* __rest
 // width, a template parameter so the ballot ranking unrolls.
 // 32-bit positions: the scatter takes 86 VGPRs (5 waves / SIMD; 64-bit: 108, 4 waves): C3 1026 ->
 // 1037 it/s, scatter 19.4 -> 18.1 us.  6 waves requested (80 VGPRs, one spill): no further change.
-template <bool AUX, int BITS>
+// EXTRA 1 (the last pass of a sort whose values index a table): also writes aux_out[pos] =
+// aux_in[value], the table in the order of the sorted keys (a value >= n_max reads as 0).
+// EXTRA 2 (a first pass with identity values, at most 2^PACK_ID_BITS keys): the value of key i is
+// i | min(aux_in[i], PACK_MAX) << PACK_ID_BITS.
+template <bool AUX, int BITS, int EXTRA = 0>
 __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
     const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t* __restrict__ keys_out,
     uint32_t* __restrict__ vals_out, const uint32_t* n_dev, uint32_t n_max, int shift, uint32_t chunk,
@@ -507,7 +545,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
       const uint32_t i = t0 + wid * (SORT_ITEMS * 64) + (uint32_t)r * 64 + lane;
       const bool v = i < end;
       key[r] = v ? keys_in[i] : 0xFFFFFFFFu;
-      val[r] = v ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
+      if constexpr (EXTRA == 2) val[r] = v ? (i | (min(aux_in[i], PACK_MAX) << PACK_ID_BITS)) : 0u;
+      else val[r] = v ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
       if constexpr (AUX) aux[r] = v ? aux_in[i] : 0u;
     }
 #pragma unroll
@@ -562,6 +601,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
         keys_out[pos] = k;
         vals_out[pos] = s_val[slot];
         if constexpr (AUX) aux_out[pos] = s_aux[slot];
+        if constexpr (EXTRA == 1) {
+          const uint32_t g = s_val[slot];
+          aux_out[pos] = g < n_max ? aux_in[g] : 0u;
+        }
       }
     }
     lds_barrier();
@@ -604,13 +647,17 @@ static inline void launch_scatter(int bits, uint32_t nb, hipStream_t st, const u
 // the later passes then sort the *n_dev survivors.  Otherwise every pass sorts n (n_dev / n_max).
 // views / vstride: `views` such sorts at once, view v's arrays (every pointer argument) lying
 // v * vstride bytes after view 0's.
+// rank_table / rank_out (32-bit keys, no aux stream): in a GS_VIEWS_SCAN_GATHER == 3 build the last
+// pass also writes rank_out[r] = rank_table[value of rank r]; in a == 4 build the first pass packs
+// min(rank_table[i], PACK_MAX) into the identity value of key i (n_max <= 2^PACK_ID_BITS).
 static inline bool radix_sort_pairs(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b,
                                     bool vals_identity, const uint32_t* n_dev, uint32_t n_max, int end_bit,
                                     uint32_t* scratch, hipStream_t st, bool drop_first = false,
                                     bool hist0_ready = false, const uint32_t* aux0 = nullptr,
                                     uint32_t* aux_a = nullptr, uint32_t* aux_b = nullptr,
                                     const uint32_t* keys_in0 = nullptr, uint32_t max_blocks = SORT_MAX_BLOCKS,
-                                    int views = 1, uint64_t vstride = 0) {
+                                    int views = 1, uint64_t vstride = 0, const uint32_t* rank_table = nullptr,
+                                    uint32_t* rank_out = nullptr) {
   if (aux0 && end_bit != 32) {
     // only the 8-bit aux scatter is built (launch_scatter<true>): a second value stream needs 32-bit keys
     host_error("radix_sort_pairs: a second value stream travels only with 32-bit keys (four 8-bit passes)");
@@ -638,6 +685,19 @@ static inline bool radix_sort_pairs(uint32_t* keys_a, uint32_t* vals_a, uint32_t
     GS_LAUNCH("radix_rowscan", k_radix_rowscan<>, dim3(RADIX, views), dim3(SORT_THREADS), 0, st, hist, p.nb,
               row_total, vstride);
     const uint32_t* vsrc = (shift == 0 && vals_identity) ? nullptr : vin;
+#if GS_VIEWS_SCAN_GATHER == 3
+    if (rank_table && !aux0 && bits == 8 && shift + bits >= end_bit) {
+      // the last pass also writes rank_out[rank] = rank_table[value]
+      GS_LAUNCH("radix_scatter", (k_radix_scatter<false, 8, 1>), dim3(p.nb, views), dim3(SORT_THREADS), 0, st, kin_p,
+                vsrc, kout, vout, nd, n_max, shift, p.chunk, p.nb, hist, row_total, drop, rank_table, rank_out, vstride);
+    } else
+#elif GS_VIEWS_SCAN_GATHER == 4
+    if (rank_table && !aux0 && bits == 8 && shift == 0 && vals_identity && n_max <= (1u << PACK_ID_BITS)) {
+      // the first pass packs rank_table[i] beside the identity value i
+      GS_LAUNCH("radix_scatter", (k_radix_scatter<false, 8, 2>), dim3(p.nb, views), dim3(SORT_THREADS), 0, st, kin_p,
+                nullptr, kout, vout, nd, n_max, shift, p.chunk, p.nb, hist, row_total, drop, rank_table, nullptr, vstride);
+    } else
+#endif
     if (aux0) {
       launch_scatter<true>(bits, p.nb, st, kin_p, vsrc, kout, vout, nd, n_max, shift, p.chunk, hist, row_total, drop, ain,
                            aout, views, vstride);
