@@ -606,8 +606,9 @@ static int render_tail(int P, const CameraArgs& c, const FwdOut& o, unsigned mod
 enum class Totals { ReadBack, Bounded, Counted };
 // The single-view forward: validation, the preprocess and the ordering, then what `mode` asks for.
 // The order of the checks and of their side effects is part of the contract.
+// aa (gs_forward_preprocess_aa): the antialiased preprocess kernels; nothing else differs.
 static int forward_view(const GaussianArgs& g, const CameraArgs& c, const FwdOut& o, Totals mode,
-                        long long* num_rendered_host, int debug, hipStream_t st) {
+                        long long* num_rendered_host, int debug, hipStream_t st, bool aa = false) {
   const int P = g.P;
   const bool whole = mode != Totals::ReadBack;  // the binning and the render follow in this call
   clear_error(debug);
@@ -634,7 +635,7 @@ static int forward_view(const GaussianArgs& g, const CameraArgs& c, const FwdOut
   }
   GeomPtrs geo;
   geom_layout((size_t)P, &geo, (char*)o.geom);
-  fwd_preprocess(g, c, o.radii, geo, st);
+  fwd_preprocess(g, c, o.radii, geo, st, aa);
   const uint32_t cap32 = (uint32_t)o.num_rendered;
   fwd_order(P, geo, st, rb ? rb->dev : nullptr, rb ? rb->ev[0] : nullptr, whole ? &cap32 : nullptr,
             bs ? bs->dev : nullptr);
@@ -675,6 +676,21 @@ int gs_forward_preprocess(int P, int D, int M, const float* background, int W, i
                  cov3D_precomp),
       make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered),
       FwdOut{radii_out, geom_buffer}, Totals::ReadBack, num_rendered_host, debug, (hipStream_t)stream);
+}
+
+int gs_forward_preprocess_aa(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                             const float* shs, const float* colors_precomp, const float* opacities,
+                             const float* scales, float scale_modifier, const float* rotations,
+                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                             const float* campos, float tan_fovx, float tan_fovy, int prefiltered, int* radii_out,
+                             void* geom_buffer, long long* num_rendered_host, int debug, void* stream,
+                             int antialiasing) {
+  return forward_view(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, prefiltered),
+      FwdOut{radii_out, geom_buffer}, Totals::ReadBack, num_rendered_host, debug, (hipStream_t)stream,
+      antialiasing != 0);
 }
 
 int gs_forward_preprocess_split(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1068,6 +1084,7 @@ struct BwdIn {
   void* grad_buffer;
   const float* dL_dout_invdepth = nullptr;  // gs_backward_accumulate_aux (either may be null)
   const float* dL_dout_alpha = nullptr;
+  bool antialiasing = false;  // gs_backward_accumulate_aa: the forward scaled the opacities (needs g.opacities)
 };
 
 // out: the caller's gradient pointers as passed; the ones the scene's inputs cannot receive are dropped here
@@ -1076,8 +1093,9 @@ static int backward_impl(const GaussianArgs& g, const CameraArgs& c, const BwdIn
   const int P = g.P;
   const long long num_rendered = in.num_rendered;
   clear_error(debug);
-  // (the opacity is carried by the forward's splat records: not required here)
-  if (!validate(g, c, false)) return 1;
+  // (the opacity is carried by the forward's splat records: not required here; an antialiased
+  // backward chains through the scale and reads it)
+  if (!validate(g, c, in.antialiasing)) return 1;
   if (P == 0) return 0;
   if (!in.geom || !in.binning || !in.image || !in.dL_dout_color || !in.grad_buffer)
     return set_error("missing buffer pointer"), 1;
@@ -1103,7 +1121,8 @@ static int backward_impl(const GaussianArgs& g, const CameraArgs& c, const BwdIn
   if (g.cov3D) out.dscale = out.drot = nullptr;
   // the gradient outputs may be shared with views on other streams: order only this last kernel
   if (wait_event && !check_hip(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0), "hipStreamWaitEvent")) return 1;
-  bwd_preprocess(g, c, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st, aux);
+  bwd_preprocess(g, c, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st, aux,
+                 in.antialiasing);
   if (aux.on() && num_rendered > 0) {
     // the depth chain's term, added after the kernel that wrote dL_dmeans3D (same stream, behind the wait)
     bwd_depth_chain(g, c, L.geo, aux, out.dmean3D, st);
@@ -1172,6 +1191,34 @@ int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int
       wait_event, debug, (hipStream_t)stream);
 }
 
+int gs_backward_accumulate_aa(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                              const float* shs, const float* shs_rest, const float* colors_precomp,
+                              const float* opacities, const float* scales, float scale_modifier,
+                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                              const int* radii, const void* geom_buffer, long long num_rendered,
+                              const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                              const float* dL_dout_invdepth, const float* dL_dout_alpha, void* grad_buffer,
+                              float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
+                              float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                              unsigned accumulate, void* wait_event, int debug, void* stream, int antialiasing) {
+  (void)radii;
+  if (antialiasing && shs_rest) {
+    clear_error(debug);
+    return set_error("antialiasing: not supported with split SH rows (shs_rest)"), 1;
+  }
+  BwdIn in{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dout_invdepth,
+           dL_dout_alpha};
+  in.antialiasing = antialiasing != 0;
+  return backward_impl(
+      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0), in,
+      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+              accumulate},
+      wait_event, debug, (hipStream_t)stream);
+}
+
 int gs_backward_accumulate_split(int P, int D, int M, const float* background, int W, int H, const float* means3D,
                                  const float* shs_dc, const float* shs_rest, const float* opacities,
                                  const float* scales, float scale_modifier, const float* rotations,
@@ -1199,19 +1246,15 @@ int gs_backward_accumulate_split(int P, int D, int M, const float* background, i
 
 size_t gs_camera_grad_scratch_bytes(int P) { return camera_grad_scratch_bytes((size_t)(P > 0 ? P : 0)); }
 
-int gs_backward_camera(int P, int D, int M, const float* background, int W, int H, const float* means3D,
-                       const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
-                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                       float tan_fovy, const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
-                       int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
-                       int debug, void* stream) {
-  const GaussianArgs g = make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales,
-                                    scale_modifier, rotations, cov3D_precomp);
-  const CameraArgs c = make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
-  hipStream_t st = (hipStream_t)stream;
+// The camera gradient of one view behind its backward (gs_backward_camera; aa: gs_backward_camera_aa,
+// whose kernels read the opacities)
+static int backward_camera_impl(const GaussianArgs& g, const CameraArgs& c, const void* geom_buffer,
+                                long long num_rendered, const void* aux_grad_buffer, int aux_valid, void* scratch,
+                                float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, int debug,
+                                hipStream_t st, bool aa) {
+  const int P = g.P;
   clear_error(debug);
-  if (!validate(g, c, false)) return 1;
+  if (!validate(g, c, aa)) return 1;
   if (!dL_dviewmatrix || !dL_dprojmatrix) return set_error("missing gradient output pointer"), 1;
   if (P == 0) {  // no Gaussians: zero gradients
     if (!check_hip(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), st), "hipMemsetAsync") ||
@@ -1233,8 +1276,37 @@ int gs_backward_camera(int P, int D, int M, const float* background, int W, int 
   }
   // (without instances the aux backward sums nothing: no depth term, as in backward_impl)
   bwd_camera(g, c, geo, num_rendered > 0 ? gsum_aux : nullptr, (double*)scratch, dL_dviewmatrix, dL_dprojmatrix,
-             dL_dcampos, st);
+             dL_dcampos, st, aa);
   return t_failed ? 1 : 0;
+}
+
+int gs_backward_camera(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                       const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
+                       int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                       int debug, void* stream) {
+  return gs_backward_camera_aa(P, D, M, background, W, H, means3D, shs, colors_precomp, opacities, scales,
+                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                               tan_fovy, geom_buffer, num_rendered, aux_grad_buffer, aux_valid, scratch,
+                               dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, debug, stream, 0);
+}
+
+int gs_backward_camera_aa(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                          const float* shs, const float* colors_precomp, const float* opacities,
+                          const float* scales, float scale_modifier, const float* rotations,
+                          const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, float tan_fovx, float tan_fovy, const void* geom_buffer,
+                          long long num_rendered, const void* aux_grad_buffer, int aux_valid, void* scratch,
+                          float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, int debug, void* stream,
+                          int antialiasing) {
+  return backward_camera_impl(
+      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0), geom_buffer,
+      num_rendered, aux_grad_buffer, aux_valid, scratch, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, debug,
+      (hipStream_t)stream, antialiasing != 0);
 }
 
 int gs_backward_render(int P, int D, int M, const float* background, int W, int H, const float* viewmatrix,

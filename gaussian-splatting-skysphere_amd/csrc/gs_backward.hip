@@ -746,10 +746,20 @@ struct CamTerms {
   float J00, J02, J11, J12;  // the Jacobian's entries as cov2d forms them (clamped tx, ty)
   float m_w, mul1, mul2;  // the projection's 1 / w and its two quotient factors
 };
-template <bool CAM = false>
+// AA (the antialiased forward, aa_scale): the splat record carries op s, so g = dL/d(op s) -- the
+// record sum's opacity field -- chains to the opacity (dop = s g) and, through s = sqrt(r),
+// r = D0 / D, to the raw covariance: gr = dL/dr = op g / (2 s), zero where the floor holds s, and
+//   dr/dc00 = (c11 D - D0 c) / D^2,  dr/dc11 = (c00 D - D0 a) / D^2,  dr/dc01 = -2 c01 (D - D0) / D^2
+// added to dL_da / dL_dc / dL_db before anything is formed from them, so the covariance, mean and
+// camera terms below pick the chain up unchanged.
+struct AAIn {
+  float op, g;  // the Gaussian's opacity input and dL/d(op s)
+  float dop;    // out: dL/dop
+};
+template <bool CAM = false, bool AA = false>
 __device__ __forceinline__ void camera_grads(const CameraArgs& c, float px, float py, float pz, const float* cov3,
                                              float dcon0, float dcon1, float dcon2, float dm2x, float dm2y,
-                                             float* dcv, float* dmean, CamTerms* ct = nullptr) {
+                                             float* dcv, float* dmean, CamTerms* ct = nullptr, AAIn* aa = nullptr) {
 #pragma unroll
   for (int k = 0; k < 6; k++) dcv[k] = 0.f;
   // conic -> cov2D -> cov3D and view-space mean
@@ -759,10 +769,23 @@ __device__ __forceinline__ void camera_grads(const CameraArgs& c, float px, floa
   float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
   const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
   const float(*Tm)[3] = cv.T;
+  if constexpr (AA) {
+    float r, D0;
+    aa->dop = aa_scale(cv, denom, r, D0) * aa->g;
+  }
   if (denom2inv != 0.0f) {
     dL_da = denom2inv * (-Cc * Cc * dcon0 + 2.f * Bv * Cc * dcon1 + (denom - A * Cc) * dcon2);
     dL_dc = denom2inv * (-A * A * dcon2 + 2.f * A * Bv * dcon1 + (denom - A * Cc) * dcon0);
     dL_db = denom2inv * 2.f * (Bv * Cc * dcon0 - (denom + 2.f * Bv * Bv) * dcon1 + A * Bv * dcon2);
+    if constexpr (AA) {
+      float aa_r, aa_D0;
+      const float aa_s = aa_scale(cv, denom, aa_r, aa_D0);
+      const float gr = aa_r > AA_FLOOR ? (aa->op * aa->g) / (2.f * aa_s) : 0.f;
+      const float q = gr / (denom * denom);
+      dL_da = dL_da + q * (cv.c11 * denom - aa_D0 * Cc);
+      dL_dc = dL_dc + q * (cv.c00 * denom - aa_D0 * A);
+      dL_db = dL_db + q * (-2.f * Bv * (denom - aa_D0));
+    }
     dcv[0] = Tm[0][0] * Tm[0][0] * dL_da + Tm[0][0] * Tm[1][0] * dL_db + Tm[1][0] * Tm[1][0] * dL_dc;
     dcv[3] = Tm[0][1] * Tm[0][1] * dL_da + Tm[0][1] * Tm[1][1] * dL_db + Tm[1][1] * Tm[1][1] * dL_dc;
     dcv[5] = Tm[0][2] * Tm[0][2] * dL_da + Tm[0][2] * Tm[1][2] * dL_db + Tm[1][2] * Tm[1][2] * dL_dc;
@@ -829,7 +852,8 @@ __device__ __forceinline__ void gput(float* p, size_t k, float v, uint32_t acc, 
 // projection, SH (DEG >= 0: dL/dsh into `row`, see sh_backward) and scale / rotation.  Each result
 // goes to `sink` as soon as it is formed (the stores of the plain path stay where they were, which
 // keeps the values' live ranges -- and the kernels' register counts -- short).
-template <int DEG, bool REG, class Sink>
+// AA: the opacity gradient is s times the record sum's and leaves after camera_grads, which forms it.
+template <int DEG, bool REG, class Sink, bool AA = false>
 __device__ __forceinline__ void preprocess_bwd_visible(int i, const GaussianArgs& g, const CameraArgs& c,
                                                        const uint8_t* __restrict__ clamped,
                                                        const float* __restrict__ gsum, float* row, bool want_sr,
@@ -844,7 +868,7 @@ __device__ __forceinline__ void preprocess_bwd_visible(int i, const GaussianArgs
   const float dcon0 = a[5], dcon1 = a[6], dcon2 = a[7];
   sink.color(dcol);
   sink.mean2d(dm2x, dm2y);
-  sink.opacity(a[8]);
+  if constexpr (!AA) sink.opacity(a[8]);
   const float px = g.means3D[3 * i], py = g.means3D[3 * i + 1], pz = g.means3D[3 * i + 2];
   float cov3[6];
   if (g.cov3D) {
@@ -855,7 +879,13 @@ __device__ __forceinline__ void preprocess_bwd_visible(int i, const GaussianArgs
           g.rotations[4 * i + 1], g.rotations[4 * i + 2], g.rotations[4 * i + 3], cov3);
   }
   float dcv[6], dmean[3];
-  camera_grads(c, px, py, pz, cov3, dcon0, dcon1, dcon2, dm2x, dm2y, dcv, dmean);
+  if constexpr (AA) {
+    AAIn aa{g.opacities[i], a[8], 0.f};
+    camera_grads<false, true>(c, px, py, pz, cov3, dcon0, dcon1, dcon2, dm2x, dm2y, dcv, dmean, nullptr, &aa);
+    sink.opacity(aa.dop);
+  } else {
+    camera_grads(c, px, py, pz, cov3, dcon0, dcon1, dcon2, dm2x, dm2y, dcv, dmean);
+  }
   sink.cov3d(dcv);
   if (DEG >= 0) {
     float shm[3];
@@ -905,7 +935,7 @@ struct StoreSink {
   }
 };
 
-template <int DEG, bool REG = false>
+template <int DEG, bool REG = false, bool AA = false>
 __device__ __forceinline__ void preprocess_bwd_one(int i, const GaussianArgs& g, const CameraArgs& c,
                                                    const uint32_t* __restrict__ tiles,
                                                    const uint8_t* __restrict__ clamped,
@@ -945,7 +975,7 @@ __device__ __forceinline__ void preprocess_bwd_one(int i, const GaussianArgs& g,
     return;
   }
   StoreSink sink{out, i};
-  preprocess_bwd_visible<DEG, REG>(i, g, c, clamped, gsum, row, out.dscale && out.drot, sink);
+  preprocess_bwd_visible<DEG, REG, StoreSink, AA>(i, g, c, clamped, gsum, row, out.dscale && out.drot, sink);
 }
 
 // colours precomputed (no SH gradient)
@@ -956,14 +986,23 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_colors(GaussianArgs g, C
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   if (i < g.P) preprocess_bwd_one<-1>(i, g, c, tiles, clamped, gsum, out, nullptr);
 }
+// ... of an antialiased forward (gs_backward_accumulate_aa)
+__global__ __launch_bounds__(256) void k_preprocess_bwd_colors_aa(GaussianArgs g, CameraArgs c,
+                                                                  const uint32_t* __restrict__ tiles,
+                                                                  const uint8_t* __restrict__ clamped,
+                                                                  const float* __restrict__ gsum, GradOut out) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i < g.P) preprocess_bwd_one<-1, false, true>(i, g, c, tiles, clamped, gsum, out, nullptr);
+}
 
 // Register variant: the lane loads its own SH row (first 3K floats, 16-B loads when
 // the rows allow) and stores dL/dsh the same way; no LDS, so occupancy is set by registers alone.
-template <int DEG, bool SPLIT = false>  // SPLIT: SH rows from g.shs (features_dc) + g.shs_rest
-__global__ __launch_bounds__(256) void k_preprocess_bwd_reg(GaussianArgs g, CameraArgs c,
-                                                            const uint32_t* __restrict__ tiles,
-                                                            const uint8_t* __restrict__ clamped,
-                                                            const float* __restrict__ gsum, GradOut out) {
+// (the kernels' body: k_preprocess_bwd_reg, and with AA k_preprocess_bwd_reg_aa)
+template <int DEG, bool SPLIT, bool AA>  // SPLIT: SH rows from g.shs (features_dc) + g.shs_rest
+__device__ __forceinline__ void preprocess_bwd_reg_body(const GaussianArgs& g, const CameraArgs& c,
+                                                        const uint32_t* __restrict__ tiles,
+                                                        const uint8_t* __restrict__ clamped,
+                                                        const float* __restrict__ gsum, const GradOut& out) {
   constexpr int KF = 3 * (DEG + 1) * (DEG + 1);
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   if (i >= g.P) return;
@@ -996,10 +1035,10 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_reg(GaussianArgs g, Came
   // invisible: every gradient (dL/dsh too) is written as zero by this call; split from the
   // visible call so each inlined copy is specialised (measured 113 -> 109.5 us at C3)
   if (tiles[i] == 0) {
-    preprocess_bwd_one<DEG, true>(i, g, c, tiles, clamped, gsum, out, row);
+    preprocess_bwd_one<DEG, true, AA>(i, g, c, tiles, clamped, gsum, out, row);
     return;
   }
-  preprocess_bwd_one<DEG, true>(i, g, c, tiles, clamped, gsum, out, row);
+  preprocess_bwd_one<DEG, true, AA>(i, g, c, tiles, clamped, gsum, out, row);
   if (out.acc & GS_ACC_SH) {  // (uniform) multi-view accumulation: dL/dsh += this view's
     if (vec_out) {
 #pragma unroll
@@ -1023,6 +1062,22 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_reg(GaussianArgs g, Came
     for (int k = 0; k < KF; k++) dst[k] = row[k];
   }
   for (int k = KF; k < rowf; k++) dst[k] = 0.0f;
+}
+template <int DEG, bool SPLIT = false>
+__global__ __launch_bounds__(256) void k_preprocess_bwd_reg(GaussianArgs g, CameraArgs c,
+                                                            const uint32_t* __restrict__ tiles,
+                                                            const uint8_t* __restrict__ clamped,
+                                                            const float* __restrict__ gsum, GradOut out) {
+  preprocess_bwd_reg_body<DEG, SPLIT, false>(g, c, tiles, clamped, gsum, out);
+}
+// The backward of an antialiased forward (gs_backward_accumulate_aa): the register variant at every
+// degree (whole SH rows; no LDS-staged degree-3 variant), with the opacity chain of camera_grads<.., AA>.
+template <int DEG>
+__global__ __launch_bounds__(256) void k_preprocess_bwd_reg_aa(GaussianArgs g, CameraArgs c,
+                                                               const uint32_t* __restrict__ tiles,
+                                                               const uint8_t* __restrict__ clamped,
+                                                               const float* __restrict__ gsum, GradOut out) {
+  preprocess_bwd_reg_body<DEG, false, true>(g, c, tiles, clamped, gsum, out);
 }
 
 // Staged variant (degree 3 with whole 48-float rows, dL/dsh written not added):
@@ -1558,11 +1613,29 @@ void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin,
 
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
-                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux) {
+                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux, bool aa) {
   if (g.P <= 0) return;
   if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st, aux);
   dim3 grid((g.P + 255) / 256), block(256);
   const bool sh = g.colors == nullptr && g.shs != nullptr && out.dsh != nullptr;
+  if (aa) {  // whole SH rows or colours (the entry refuses split rows): the register variant at every degree
+#define GS_PBWD_AA(D)                                                                                          \
+  GS_LAUNCH("preprocess_bwd", (k_preprocess_bwd_reg_aa<D>), grid, block, 0, st, g, c, geo.tiles, geo.clamped, \
+            geo.gsum, out)
+    if (!sh) {
+      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_colors_aa, grid, block, 0, st, g, c, geo.tiles, geo.clamped,
+                geo.gsum, out);
+      return;
+    }
+    switch (g.D) {
+      case 0: GS_PBWD_AA(0); break;
+      case 1: GS_PBWD_AA(1); break;
+      case 2: GS_PBWD_AA(2); break;
+      default: GS_PBWD_AA(3); break;
+    }
+#undef GS_PBWD_AA
+    return;
+  }
   if (!sh) {
     GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_colors, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum,
               out);
@@ -1625,7 +1698,11 @@ void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& 
 // one thread adds the 8 segments, and the workgroup writes one row of CAMG_ROW doubles.
 // -DGS_CAMGRAD_BUTTERFLY builds the wave xor-butterfly of fp64 values instead (measured slower:
 // profiles/camera_grad_reduce_ab.txt).
-template <int DEG>  // -1: no campos sums (no SH row read)
+// AA (the camera gradient of an antialiased forward, gs_backward_camera_aa): camera_grads<true, true>
+// adds the opacity scale's chain to the covariance gradient the terms are formed from.  (A template
+// parameter of the kernel itself: a shared body inlined into two kernels moved k_camera_grad<1>'s
+// register counts.)
+template <int DEG, bool AA = false>  // DEG -1: no campos sums (no SH row read)
 __global__ __launch_bounds__(256) void k_camera_grad(GaussianArgs g, CameraArgs c,
                                                      const uint32_t* __restrict__ tiles,
                                                      const uint8_t* __restrict__ clamped,
@@ -1656,7 +1733,12 @@ __global__ __launch_bounds__(256) void k_camera_grad(GaussianArgs g, CameraArgs 
     }
     float dcv[6], dmean[3];
     CamTerms ct;
-    camera_grads<true>(c, px, py, pz, cov3, a[5], a[6], a[7], dm2x, dm2y, dcv, dmean, &ct);
+    if constexpr (AA) {
+      AAIn aa{g.opacities[i], a[8], 0.f};
+      camera_grads<true, true>(c, px, py, pz, cov3, a[5], a[6], a[7], dm2x, dm2y, dcv, dmean, &ct, &aa);
+    } else {
+      camera_grads<true>(c, px, py, pz, cov3, a[5], a[6], a[7], dm2x, dm2y, dcv, dmean, &ct);
+    }
     float dz = 0.0f;
     if (gsum_aux) {
       const float z = splat[3 * i + 2].y;
@@ -1786,14 +1868,20 @@ __global__ __launch_bounds__(1024) void k_camera_grad_finish(const uint32_t* __r
 }
 
 void bwd_camera(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const float* gsum_aux,
-                double* partial, float* dview, float* dproj, float* dcampos, hipStream_t st) {
+                double* partial, float* dview, float* dproj, float* dcampos, hipStream_t st, bool aa) {
   if (g.P <= 0) return;
   const int nb = (g.P + 255) / 256;
   const dim3 grid(nb), block(256);
   const int deg = (dcampos && g.shs && !g.colors) ? g.D : -1;
-#define GS_CAMG(D)                                                                                            \
-  GS_LAUNCH("camera_grad", k_camera_grad<D>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, gsum_aux, \
-            geo.splat, partial)
+#define GS_CAMG(D)                                                                                                  \
+  do {                                                                                                              \
+    if (aa)                                                                                                         \
+      GS_LAUNCH("camera_grad", (k_camera_grad<D, true>), grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum,      \
+                gsum_aux, geo.splat, partial);                                                                      \
+    else                                                                                                            \
+      GS_LAUNCH("camera_grad", k_camera_grad<D>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, gsum_aux, \
+                geo.splat, partial);                                                                                \
+  } while (0)
   switch (deg) {
     case 0: GS_CAMG(0); break;
     case 1: GS_CAMG(1); break;

@@ -355,6 +355,7 @@ __device__ __forceinline__ void cov3d(float sx, float sy, float sz, float mod, f
 // product T = J Rw and the view-space point (clamped x, y).
 struct Cov2D {
   float a, b, c;
+  float c00, c11;  // the diagonal before the dilation (antialiasing: aa_scale)
   float T[2][3];
   float tx, ty, tz;
   float gmx, gmy;  // 0 where the tx/tz (ty/tz) frustum clamp was active
@@ -391,10 +392,25 @@ __device__ __forceinline__ Cov2D cov2d(const float* view, float px, float py, fl
   o.a = c00 + 0.3f;
   o.b = c01;
   o.c = c11 + 0.3f;
+  o.c00 = c00;
+  o.c11 = c11;
   o.tx = t.x;
   o.ty = t.y;
   o.tz = t.z;
   return o;
+}
+
+// Antialiasing (opt-in): the dilation spreads a splat over det(S + 0.3 I) / det S
+// times its area, so its opacity is scaled by s = sqrt(det S / det(S + 0.3 I)), the Mip-Splatting
+// 2D filter normalisation with upstream's floor.  D: the dilated determinant a c - b b as the
+// caller formed it (preprocess_view's det, camera_grads' denom: the same expression on the same
+// cov2d() values, so the forward and the backward see the same bits).  Also hands out the ratio r
+// (the floor's condition) and D0 = det S for the backward's chain.
+constexpr float AA_FLOOR = 0.000025f;
+__device__ __forceinline__ float aa_scale(const Cov2D& cv, float D, float& r, float& D0) {
+  D0 = cv.c00 * cv.c11 - cv.b * cv.b;
+  r = D0 / D;
+  return sqrtf(fmaxf(AA_FLOOR, r));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -170,7 +170,9 @@ __device__ __forceinline__ PreShared<DEG, SRC> preprocess_shared(int i, const Ga
 // What one camera adds for Gaussian i: near cull, projection, EWA cov2D -> conic, radius and tile
 // rectangle, SH -> RGB, the tile-exact row spans, and the stores of the view's outputs.  Returns the
 // number of tiles the Gaussian touches (0 when culled; radii[i] and tiles[i] are then 0).
-template <int DEG, int SRC, bool HOIST>
+// AA (k_preprocess_aa): the antialiased opacity op s takes the opacity's place in the splat record
+// and in the culling limit (aa_scale); everything else is the plain code.
+template <int DEG, int SRC, bool HOIST, bool AA = false>
 __device__ __forceinline__ uint32_t preprocess_view(int i, const PreShared<DEG, SRC>& sh, const GaussianArgs& g,
                                                     const CameraArgs& c,
                                                     int* __restrict__ radii, float4* __restrict__ splat,
@@ -232,8 +234,15 @@ __device__ __forceinline__ uint32_t preprocess_view(int i, const PreShared<DEG, 
       sh_rgb_of<DEG, SRC>(i, g, dx / len, dy / len, dz / len, rgb, cl);
     }
   }
-  const float op = HOIST ? sh.op : g.opacities[i];
-  const float lim = HOIST ? sh.lim : cull_lim(op);
+  float op = HOIST ? sh.op : g.opacities[i];
+  float lim;
+  if constexpr (AA) {
+    float r, D0;
+    op = op * aa_scale(cv, det, r, D0);
+    lim = cull_lim(op);
+  } else {
+    lim = HOIST ? sh.lim : cull_lim(op);
+  }
   splat[3 * i + 0] = make_float4(sx, sy, cxx, cxy);
   splat[3 * i + 1] = make_float4(cyy, op, rgb[0], rgb[1]);
   splat[3 * i + 2] = make_float4(rgb[2], pv.z, lim, 0.0f);
@@ -299,7 +308,7 @@ __device__ __forceinline__ const float* stage_block_rows(const GaussianArgs& g, 
 // go to its WgTotals slot (workgroup_totals).  depth_key[i] is the depth's bits for those and
 // DEPTH_DROP for every other Gaussian: the first depth-sort pass drops them, which is the
 // visibility compaction.
-template <int DEG, int SRC>
+template <int DEG, int SRC, bool AA = false>
 __device__ __forceinline__ void preprocess_block(const GaussianArgs& g, const CameraArgs& c, int* __restrict__ radii,
                                                  float4* __restrict__ splat, float4* __restrict__ binrec,
                                                  uint32_t* __restrict__ depth_key, uint32_t* __restrict__ tiles,
@@ -309,7 +318,7 @@ __device__ __forceinline__ void preprocess_block(const GaussianArgs& g, const Ca
   bool culled = false;
   if (i < g.P) {
     const PreShared<DEG, SRC> sh = preprocess_shared<DEG, SRC, false>(i, g, nullptr);
-    area = preprocess_view<DEG, SRC, false>(i, sh, g, c, radii, splat, binrec, dbits, tiles, clamped, culled);
+    area = preprocess_view<DEG, SRC, false, AA>(i, sh, g, c, radii, splat, binrec, dbits, tiles, clamped, culled);
     depth_key[i] = area ? dbits : DEPTH_DROP;
   }
   workgroup_totals(area, culled, wg, (uint32_t)b);
@@ -322,6 +331,16 @@ __global__ __launch_bounds__(256) void k_preprocess(GaussianArgs g, CameraArgs c
                                                     uint32_t* __restrict__ tiles, uint8_t* __restrict__ clamped,
                                                     WgTotals* __restrict__ wg) {
   preprocess_block<DEG, ROW_GLOBAL>(g, c, radii, splat, binrec, depth_key, tiles, clamped, wg);
+}
+
+// The antialiased preprocess (gs_forward_preprocess_aa): k_preprocess's body with the opacity scaled.
+template <int DEG>
+__global__ __launch_bounds__(256) void k_preprocess_aa(GaussianArgs g, CameraArgs c, int* __restrict__ radii,
+                                                       float4* __restrict__ splat, float4* __restrict__ binrec,
+                                                       uint32_t* __restrict__ depth_key,
+                                                       uint32_t* __restrict__ tiles, uint8_t* __restrict__ clamped,
+                                                       WgTotals* __restrict__ wg) {
+  preprocess_block<DEG, ROW_GLOBAL, true>(g, c, radii, splat, binrec, depth_key, tiles, clamped, wg);
 }
 
 // The split-SH preprocess: k_preprocess's body with the split row loader (ROW_SPLIT).  Five waves
@@ -363,13 +382,29 @@ static void launch_row_chunks(const GaussianArgs& g, hipStream_t st, Launch&& la
   }
 }
 
-void fwd_preprocess(const GaussianArgs& g0, const CameraArgs& c, int* radii, const GeomPtrs& geo, hipStream_t st) {
-  launch_row_chunks(g0, st, [&](const GaussianArgs& g, dim3 grid) { fwd_preprocess_grid(g, c, radii, geo, st, grid); });
+void fwd_preprocess(const GaussianArgs& g0, const CameraArgs& c, int* radii, const GeomPtrs& geo, hipStream_t st,
+                    bool aa) {
+  launch_row_chunks(g0, st,
+                    [&](const GaussianArgs& g, dim3 grid) { fwd_preprocess_grid(g, c, radii, geo, st, grid, aa); });
 }
 
 void fwd_preprocess_grid(const GaussianArgs& g, const CameraArgs& c, int* radii, const GeomPtrs& geo, hipStream_t st,
-                         dim3 grid) {
+                         dim3 grid, bool aa) {
   const dim3 block(256);
+  if (aa) {  // whole SH rows or colours (the entry refuses split rows)
+#define GS_PRE_AA(D)                                                                                             \
+  GS_LAUNCH("preprocess", (k_preprocess_aa<D>), grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, \
+            geo.tiles, geo.clamped, geo.wg_tot)
+    switch (g.colors ? -1 : g.D) {
+      case -1: GS_PRE_AA(-1); break;
+      case 0: GS_PRE_AA(0); break;
+      case 1: GS_PRE_AA(1); break;
+      case 2: GS_PRE_AA(2); break;
+      default: GS_PRE_AA(3); break;
+    }
+#undef GS_PRE_AA
+    return;
+  }
   if (g.colors) {
     GS_LAUNCH("preprocess", k_preprocess<-1>, grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, geo.tiles,
               geo.clamped, geo.wg_tot);

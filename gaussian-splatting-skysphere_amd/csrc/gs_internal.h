@@ -445,9 +445,11 @@ __device__ __forceinline__ void timing_record(unsigned long long (*buf)[5], unsi
 #endif
 
 // ---- stages (gs_forward.hip / gs_backward.hip) ----
-void fwd_preprocess(const GaussianArgs& g, const CameraArgs& c, int* radii, const GeomPtrs& geo, hipStream_t st);
+// aa: the antialiased kernels (the opacity scaled by aa_scale; whole SH rows or colours only)
+void fwd_preprocess(const GaussianArgs& g, const CameraArgs& c, int* radii, const GeomPtrs& geo, hipStream_t st,
+                    bool aa = false);
 void fwd_preprocess_grid(const GaussianArgs& g, const CameraArgs& c, int* radii, const GeomPtrs& geo, hipStream_t st,
-                         dim3 grid);
+                         dim3 grid, bool aa = false);
 // Row waits of this thread (gs_set_row_waits): chunk k covers the rows below `hi` not covered by an
 // earlier chunk and must wait for `ev` (null: nothing to wait for).  take_row_waits() moves them out
 // (the next forward preprocess consumes them); stream_wait() is hipStreamWaitEvent with the error
@@ -551,7 +553,8 @@ void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin,
                  const BwdAux& aux = BwdAux());
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
-                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux = BwdAux());
+                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux = BwdAux(),
+                    bool aa = false);  // aa: the view's forward was antialiased (g.opacities is read)
 // the aux backward's per-Gaussian tail, after the kernel that writes the gradients: the depth
 // chain's add into dL/dmeans3D (from gsum_aux, summed with the other record sums)
 void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BwdAux& aux,
@@ -565,7 +568,7 @@ inline size_t camera_grad_scratch_bytes(size_t P) {
   return ((P ? P : 1) + 255) / 256 * CAMG_ROW * sizeof(double);
 }
 void bwd_camera(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const float* gsum_aux,
-                double* partial, float* dview, float* dproj, float* dcampos, hipStream_t st);
+                double* partial, float* dview, float* dproj, float* dcampos, hipStream_t st, bool aa = false);
 void knn_mean_dist2(int P, const float* pts, float* out, char* scratch, hipStream_t st);
 void ssim_forward(int planes, int H, int W, const float* win11, const float* img1, const float* img2, float* dmaps,
                   float* partial, float* plane_sum, hipStream_t st);

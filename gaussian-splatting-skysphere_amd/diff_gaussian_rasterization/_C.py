@@ -146,18 +146,23 @@ class _Inputs:
     def camera(self, tan_fovx, tan_fovy):
         return (_ptr(self.view), _ptr(self.proj), _ptr(self.campos), float(tan_fovx), float(tan_fovy))
 
-    def preprocess(self, W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug, st):
-        """The two-call forward's first half (gs_forward_preprocess; _split for split SH rows):
-        (num_rendered, radii, geomBuffer), every radius written by the kernels."""
+    def preprocess(self, W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug, st,
+                   antialiasing=False):
+        """The two-call forward's first half (gs_forward_preprocess; _split for split SH rows; _aa for
+        an antialiased call): (num_rendered, radii, geomBuffer), every radius written by the kernels."""
         radii = torch.empty((self.P,), dtype=torch.int32, device=self.device)
         geom = torch.empty((_lib.gs_geom_buffer_bytes(self.P),), dtype=torch.uint8, device=self.device)
         nr = ctypes.c_longlong(0)
         split = self.sh_rest is not None
+        if antialiasing and split:
+            raise RuntimeError("antialiasing: not supported with sh_split=")
+        fn = (_lib.gs_forward_preprocess_aa if antialiasing
+              else _lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)
         _native.check(
-            (_lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)(
-                self.P, int(degree), self.M, _ptr(self.bg), W, H,
-                *self.scene(scale_modifier, self.sh_rest if split else self.colors), *self.camera(tan_fovx, tan_fovy),
-                int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st),
+            fn(self.P, int(degree), self.M, _ptr(self.bg), W, H,
+               *self.scene(scale_modifier, self.sh_rest if split else self.colors), *self.camera(tan_fovx, tan_fovy),
+               int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st,
+               *((1,) if antialiasing else ())),
             "rasterize_gaussians (preprocess)")
         _LAST_NUM_RENDERED[0] = int(nr.value)
         return int(nr.value), radii, geom
@@ -338,9 +343,13 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
 
 def _forward_ctypes(x, H, W, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug, prepared=None,
-                    capacity=None, aux=False):
+                    capacity=None, aux=False, antialiasing=False):
     """The forward of validated inputs over ctypes: rasterize_gaussians' six values, and with aux
-    (the two-call path only) the render's (invdepth [1, H, W], alpha [1, H, W]) behind them."""
+    (the two-call path only) the render's (invdepth [1, H, W], alpha [1, H, W]) behind them.
+    antialiasing (the two-call path only): the preprocess scales the opacities (gs_forward_preprocess_aa)."""
+    if antialiasing and (prepared is not None or capacity is not None):
+        raise RuntimeError("antialiasing: not supported with " + ("prepared=" if prepared is not None
+                                                                  else "binning_capacity="))
     dev = x.device
     u8 = dict(dtype=torch.uint8, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -386,7 +395,7 @@ def _forward_ctypes(x, H, W, degree, scale_modifier, tan_fovx, tan_fovy, prefilt
                 return num_rendered, out_color, radii, geom, binning, img
         else:
             num_rendered, radii, geom = x.preprocess(W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered,
-                                                     debug, st)
+                                                     debug, st, antialiasing=antialiasing)
         binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
         if aux:
@@ -412,6 +421,19 @@ def rasterize_gaussians_aux(background, means3D, colors, opacity, scales, rotati
                            prefiltered, debug, aux=True)
 
 
+def rasterize_gaussians_aa(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                           viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                           prefiltered, debug, aux=False):
+    """rasterize_gaussians with antialiasing (gs_forward_preprocess_aa): every splat's opacity is scaled
+    by sqrt(det cov2D / det(cov2D + 0.3 I)) (floor 0.005) where it enters the splat record and the
+    culling limit; with aux also rasterize_gaussians_aux's two planes.  Always the two-call path over
+    ctypes; the backward of such a forward is backward_impl(..., aa_opacity=opacity)."""
+    x = _Inputs(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
+                campos)
+    return _forward_ctypes(x, int(image_height), int(image_width), degree, scale_modifier, tan_fovx, tan_fovy,
+                           prefiltered, debug, aux=bool(aux), antialiasing=True)
+
+
 def binning_layout_count(R, binningBuffer, W, H):
     """The instance count binningBuffer is laid out for, which the C-ABI calls take as num_rendered:
     R for a buffer of gs_binning_buffer_bytes(R) bytes (the two-call, bounded and prepared
@@ -435,7 +457,7 @@ GS_ACC = {n: 1 << k for k, n in enumerate(GRAD_NAMES)}
 def backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                   projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                   imageBuffer, debug, want_all=True, sinks=None, wait_event=None, sh_rest=None, aux_grads=None,
-                  camera=None):
+                  camera=None, aa_opacity=None):
     """Shared backward.  With want_all=False the gradients that no autograd input can receive
     (colours when SHs drive the colour, cov3D when scale/rotation drive it, ...) are None and
     not computed.  sinks: {name: (buffer, accumulate)} -- that gradient is written into (or, with
@@ -448,18 +470,25 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     None (gs_backward_accumulate_aux, over ctypes).
     camera: None, or whether dL/dcampos is wanted -- the return then ends with one more item, the
     view's camera gradients (dL_dviewmatrix [4, 4], dL_dprojmatrix [4, 4], dL_dcampos [3] or None) of
-    gs_backward_camera, run right behind the backward on its stream (over ctypes)."""
+    gs_backward_camera, run right behind the backward on its stream (over ctypes).
+    aa_opacity: the opacities [P, 1] of a rasterize_gaussians_aa forward -- the backward of an antialiased
+    view (gs_backward_accumulate_aa / gs_backward_camera_aa, over ctypes), which chains through the
+    opacity scale and so reads them; None: a plain forward's backward."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None
+    antialiasing = aa_opacity is not None
+    if antialiasing and sh_rest is not None:
+        raise RuntimeError("antialiasing: not supported with sh_split=")
     if camera is not None and sh_rest is not None:
         raise RuntimeError("camera_grads: not supported with split SH rows (sh_split=)")
-    if _EXT is not None and not want_all and means3D.is_cuda and aux_grads is None and camera is None:
+    if (_EXT is not None and not want_all and means3D.is_cuda and aux_grads is None and camera is None
+            and not antialiasing):
         return _EXT.backward(background, means3D, radii, colors, scales, rotations, float(scale_modifier),
                              cov3D_precomp, viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color,
                              sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, bool(debug),
                              sh_rest, sinks or {}, wait_event.cuda_event if wait_event is not None else 0)
-    x = _Inputs(background, means3D, colors, None, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
-                campos, need_opacity=False, sh_rest=sh_rest)
+    x = _Inputs(background, means3D, colors, aa_opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
+                campos, need_opacity=antialiasing, sh_rest=sh_rest)
     P, dev = x.P, x.device
     f32 = dict(dtype=torch.float32, device=dev)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
@@ -513,17 +542,24 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
         grads = [_ptr(o[n]) for n in GRAD_NAMES]
         tail = (acc, wait, int(bool(debug)), st)
         what = "rasterize_gaussians_backward"
+        d_inv = d_alpha = None
         if aux_grads is not None:
             d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
             for t in (d_inv, d_alpha):
                 if t is not None and t.numel() != H * W:
                     raise RuntimeError("aux gradients must have shape (1, H, W)")
             grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes_aux(R, P),), dtype=torch.uint8, device=dev)
-            rc = _lib.gs_backward_accumulate_aux(*head, *x.scene(scale_modifier, x.sh_rest, x.colors), *bufs,
-                                                 _ptr(d_inv), _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail)
             what += " (aux outputs)"
         else:
             grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes(R),), dtype=torch.uint8, device=dev)
+        if antialiasing:
+            rc = _lib.gs_backward_accumulate_aa(*head, *x.scene(scale_modifier, None, x.colors), *bufs, _ptr(d_inv),
+                                                _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail, 1)
+            what += " (antialiasing)"
+        elif aux_grads is not None:
+            rc = _lib.gs_backward_accumulate_aux(*head, *x.scene(scale_modifier, x.sh_rest, x.colors), *bufs,
+                                                 _ptr(d_inv), _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail)
+        else:
             if x.sh_rest is not None:
                 rc = _lib.gs_backward_accumulate_split(*head, *x.scene(scale_modifier, x.sh_rest), *bufs,
                                                        _ptr(grad_scratch), grads[0], *grads[2:], *tail)
@@ -533,12 +569,13 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
         _native.check(rc, what)
         if camera is not None:
             cam_scratch = torch.empty((_lib.gs_camera_grad_scratch_bytes(P),), dtype=torch.uint8, device=dev)
-            rc = _lib.gs_backward_camera(*head, *x.scene(scale_modifier, x.colors), *x.camera(tan_fovx, tan_fovy),
-                                         _ptr(geomBuffer), int(R), _ptr(grad_scratch) if aux_grads is not None else None,
-                                         int(aux_grads is not None), _ptr(cam_scratch), _ptr(cam_out),
-                                         ctypes.c_void_p(cam_out.data_ptr() + 64),
-                                         ctypes.c_void_p(cam_out.data_ptr() + 128) if camera else None,
-                                         int(bool(debug)), st)
+            cam_fn = _lib.gs_backward_camera_aa if antialiasing else _lib.gs_backward_camera
+            rc = cam_fn(*head, *x.scene(scale_modifier, x.colors), *x.camera(tan_fovx, tan_fovy),
+                        _ptr(geomBuffer), int(R), _ptr(grad_scratch) if aux_grads is not None else None,
+                        int(aux_grads is not None), _ptr(cam_scratch), _ptr(cam_out),
+                        ctypes.c_void_p(cam_out.data_ptr() + 64),
+                        ctypes.c_void_p(cam_out.data_ptr() + 128) if camera else None,
+                        int(bool(debug)), st, *((1,) if antialiasing else ()))
             _native.check(rc, "rasterize_gaussians_backward (camera gradients)")
     return ret
 

@@ -13,6 +13,8 @@ Public surface used by the reference's render adapter
         -> (color, radii, invdepth [1, H, W] fp32, alpha [1, H, W] fp32)
     GaussianRasterizer(raster_settings)(..., camera_grads=True)     (extension)
         -> the same outputs; settings.viewmatrix / .projmatrix / .campos receive gradients
+    GaussianRasterizer(raster_settings)(..., antialiasing=True)     (extension; later upstream's switch)
+        -> the same outputs, every splat's opacity compensated for the 0.3 px^2 dilation
     GaussianRasterizer.markVisible(positions) -> bool [P]
     rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings)
@@ -130,9 +132,10 @@ class GaussianRasterizationSettings(NamedTuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, prepared=None, sh_split=None, binning_capacity=None):
+                        raster_settings, prepared=None, sh_split=None, binning_capacity=None, antialiasing=False):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, prepared, sh_split, binning_capacity)
+                                     cov3Ds_precomp, raster_settings, prepared, sh_split, binning_capacity,
+                                     bool(antialiasing))
 
 
 # ------------------------------------------------------------------------------------------
@@ -259,12 +262,26 @@ def _run_with_snapshot(fn, args, debug, dump_name, phase):
         raise
 
 
+def _antialiasing_refusal(prepared=None, binning_capacity=None, sh_split=None):
+    """The paths an antialiased call cannot take: their kernels (k_preprocess_views, the bounded
+    forwards, the split-row loaders) do not scale the opacity."""
+    for name, v in (("prepared", prepared), ("binning_capacity", binning_capacity), ("sh_split", sh_split)):
+        if v is not None:
+            raise RuntimeError(f"antialiasing: not supported with {name}=")
+
+
+_T_AA_DEFER = ("antialiasing: not supported with a deferring gradient owner (GradBucket(defer=True), the fused "
+               "backward + Adam of gs_train_step)")
+
+
 def _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s,
-                  prepared=None, sh_split=None, binning_capacity=None, aux=False):
+                  prepared=None, sh_split=None, binning_capacity=None, aux=False, antialiasing=False):
     """The forward of the three autograd Functions: the native call (plain, with split SH rows or a
-    binning capacity, over a prepared view, or with the aux outputs), everything the backward needs
-    on `ctx`, and the call's gradient sinks.  -> (color, radii), or with aux (color, radii, invdepth,
-    alpha)."""
+    binning capacity, over a prepared view, with the aux outputs, or antialiased), everything the
+    backward needs on `ctx`, and the call's gradient sinks.  -> (color, radii), or with aux (color,
+    radii, invdepth, alpha)."""
+    if antialiasing:
+        _antialiasing_refusal(prepared, binning_capacity, sh_split)
     # the camera matrices arrive transposed (cameras.py:54-56 world_view_transform is a
     # .transpose(0, 1) view); make them contiguous once and reuse them in backward
     view, proj = _contiguous_matrix(s.viewmatrix), _contiguous_matrix(s.projmatrix)
@@ -290,6 +307,10 @@ def _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
         tri = prepared.take(s, (means3D, nz(sh), nz(colors_precomp), opacities, nz(scales), nz(rotations),
                                 nz(cov3Ds_precomp)))
         out = _C.rasterize_gaussians(*args, prepared=tri)
+    elif antialiasing:
+        # (the snapshot's arguments end with the flag)
+        out = _run_with_snapshot(lambda *a: _C.rasterize_gaussians_aa(*a[:-1], aux=aux), args + (True,), s.debug,
+                                 "snapshot_fw.dump", "forward")
     else:
         if aux:
             fn = lambda *a: _C.rasterize_gaussians_aux(*a, sh_rest=sh_rest)  # noqa: E731
@@ -302,13 +323,15 @@ def _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     ctx.raster_settings = s
     ctx.num_rendered = num_rendered
     ctx.matrices = (view, proj)
+    ctx.antialiasing = bool(antialiasing)
     ctx.sh_rest = sh_rest
     # the split rows are kept outside save_for_backward (they are not inputs of the Function):
     # their version counters stand in for autograd's in-place check
     ctx.sh_split_versions = None if sh_rest is None else (sh._version, sh_rest._version)
     ctx.set_materialize_grads(False)  # no zero-filled gradient for the (int) radii output, or an unused one
+    # (an antialiased backward chains through the opacity scale: it reads the opacities too)
     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                          binningBuffer, imgBuffer)
+                          binningBuffer, imgBuffer, *((opacities,) if antialiasing else ()))
     ctx.mark_non_differentiable(radii)
     sinks = []
     if _SINKS:
@@ -341,7 +364,8 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
         return (None,) * 8, None
     s = ctx.raster_settings
     colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = (
-        ctx.saved_tensors)
+        ctx.saved_tensors[:10])
+    antialiasing = getattr(ctx, "antialiasing", False)
     if ctx.sh_rest is not None and (sh._version, ctx.sh_rest._version) != ctx.sh_split_versions:
         raise RuntimeError("sh_split: features_dc or features_rest was modified by an inplace operation between "
                            "the forward and the backward")
@@ -356,6 +380,9 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
     # when every parameter gradient the call needs goes to it: only the per-tile half and
     # dL_dmeans2D run now, the per-Gaussian half later for all of its views in one pass
     deferrer = _deferring_owner(ctx)
+    if deferrer is not None and antialiasing:
+        # its per-Gaussian half (k_backward_gaussians, the fused backward + Adam) has no opacity-scale chain
+        raise RuntimeError(_T_AA_DEFER)
     if deferrer is not None and ctx.sh_rest is not None and not getattr(deferrer, "accepts_sh_split", False):
         raise RuntimeError("sh_split: not supported with a deferring gradient bucket")
     if deferrer is not None:
@@ -399,7 +426,15 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
         return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
                                 aux_grads=aux_grads, camera=camera)
 
-    res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
+    def _bwd_aa(*a):  # (the snapshot's arguments end with the flag and the opacities)
+        return _C.backward_impl(*a[:-2], want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
+                                aux_grads=aux_grads, camera=camera, aa_opacity=a[-1])
+
+    if antialiasing:
+        res = _run_with_snapshot(_bwd_aa, args + (True, ctx.saved_tensors[10]), s.debug, "snapshot_bw.dump",
+                                 "backward")
+    else:
+        res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
     (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
      grad_rotations) = res[:8]
     for o in owners:
@@ -415,13 +450,13 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, prepared=None, sh_split=None, binning_capacity=None):
+                raster_settings, prepared=None, sh_split=None, binning_capacity=None, antialiasing=False):
         return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, prepared, sh_split, binning_capacity)
+                             raster_settings, prepared, sh_split, binning_capacity, antialiasing=antialiasing)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
-        return _backward_step(ctx, grad_out_color)[0] + (None,) * 4
+        return _backward_step(ctx, grad_out_color)[0] + (None,) * 5
 
 
 # ------------------------------------------------------------------------------------------
@@ -436,18 +471,18 @@ class _RasterizeGaussians(torch.autograd.Function):
 # bounded forwards and deferring gradient owners that do not opt in (owner.accepts_aux) are refused.
 # ------------------------------------------------------------------------------------------
 def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                            raster_settings, sh_split=None):
+                            raster_settings, sh_split=None, antialiasing=False):
     """-> (color, radii, invdepth, alpha)"""
     return _RasterizeGaussiansAux.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                        cov3Ds_precomp, raster_settings, sh_split)
+                                        cov3Ds_precomp, raster_settings, sh_split, bool(antialiasing))
 
 
 class _RasterizeGaussiansAux(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, sh_split=None):
+                raster_settings, sh_split=None, antialiasing=False):
         return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, sh_split=sh_split, aux=True)
+                             raster_settings, sh_split=sh_split, aux=True, antialiasing=antialiasing)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_invdepth, grad_alpha):
@@ -458,7 +493,7 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                 and not getattr(deferrer, "accepts_aux", False)):
             raise RuntimeError("aux_outputs: an alpha / inverse-depth gradient is not supported with a deferring "
                                "gradient owner (GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
-        return _backward_step(ctx, grad_out_color, (grad_invdepth, grad_alpha))[0] + (None, None)
+        return _backward_step(ctx, grad_out_color, (grad_invdepth, grad_alpha))[0] + (None, None, None)
 
 
 # ------------------------------------------------------------------------------------------
@@ -474,12 +509,12 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
 class _RasterizeGaussiansCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                viewmatrix, projmatrix, campos, raster_settings, aux):
+                viewmatrix, projmatrix, campos, raster_settings, aux, antialiasing=False):
         # (viewmatrix, projmatrix, campos are raster_settings' own tensors: inputs for the graph's sake)
         ctx.camera_aux = aux
         ctx.camera_meta = tuple((t.shape, t.device) for t in (viewmatrix, projmatrix, campos))
         return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, aux=aux)
+                             raster_settings, aux=aux, antialiasing=antialiasing)
 
     @staticmethod
     def backward(ctx, *grad_outs):
@@ -494,7 +529,7 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 shape, device = ctx.camera_meta[k]
                 if g is not None and ctx.needs_input_grad[8 + k]:
                     cam[k] = g.reshape(shape).to(device)
-        return grads + tuple(cam) + (None, None)
+        return grads + tuple(cam) + (None, None, None)
 
 
 def _deferring_owner(ctx):
@@ -524,7 +559,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, prepared=None, sh_split=None, binning_capacity=None, aux_outputs=False,
-                camera_grads=False):
+                camera_grads=False, antialiasing=False):
         """prepared: this call's PreparedView from prepare_views (extension; default: none).
         binning_capacity: size the binning buffer for that many instances and run the forward
         without a host wait (extension, ABI v10; see bounded_status()).
@@ -537,8 +572,17 @@ class GaussianRasterizer(nn.Module):
         with prepared= or binning_capacity=).
         camera_grads: settings.viewmatrix / .projmatrix / .campos that require grad receive their
         gradients (extension; with or without aux_outputs; not with prepared=, binning_capacity=,
-        sh_split= or a deferring gradient owner).  None of them requiring grad: the call without it."""
+        sh_split= or a deferring gradient owner).  None of them requiring grad: the call without it.
+        antialiasing: compensate every splat's opacity for the 0.3 px^2 low-pass dilation of its
+        footprint, op' = op sqrt(det S / det(S + 0.3 I)) (floor 0.005; later upstream revisions'
+        `antialiasing` switch, the Mip-Splatting 2D filter normalisation), so a splat smaller than a
+        pixel keeps its energy at any resolution; gradients chain through the scale (extension; with
+        or without aux_outputs / camera_grads; not with prepared=, binning_capacity=, sh_split= or a
+        deferring gradient owner).  False: today's kernels and bits."""
         s = self.raster_settings
+        antialiasing = bool(antialiasing)
+        if antialiasing:
+            _antialiasing_refusal(prepared, binning_capacity, sh_split)
         if camera_grads:
             for name, v in (("prepared", prepared), ("binning_capacity", binning_capacity), ("sh_split", sh_split)):
                 if v is not None:
@@ -564,9 +608,9 @@ class GaussianRasterizer(nn.Module):
         if camera_grads:
             return _RasterizeGaussiansCamera.apply(means3D, means2D, shs, colors_precomp, opacities, scales,
                                                    rotations, cov3D_precomp, s.viewmatrix, s.projmatrix, s.campos, s,
-                                                   bool(aux_outputs))
+                                                   bool(aux_outputs), antialiasing)
         if aux_outputs:
             return rasterize_gaussians_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                           cov3D_precomp, s, sh_split)
+                                           cov3D_precomp, s, sh_split, antialiasing)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   s, prepared, sh_split, binning_capacity)
+                                   s, prepared, sh_split, binning_capacity, antialiasing)

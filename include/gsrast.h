@@ -81,6 +81,10 @@ extern "C" {
  * Adam with the inverse depth's chain into dL/dmeans3D). */
 #define GSRAST_HAS_AUX_DEFERRED 1
 
+/* Antialiasing, the opacity compensation of the 0.3 px^2 dilation (additive, same ABI version):
+ * gs_forward_preprocess_aa, gs_backward_accumulate_aa, gs_backward_camera_aa. */
+#define GSRAST_HAS_ANTIALIASING 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -383,6 +387,59 @@ int gs_backward_camera(int P, int D, int M, const float* background, int image_w
                        const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
                        int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
                        float* dL_dcampos, int debug, void* stream);
+
+/* ---- antialiasing (GSRAST_HAS_ANTIALIASING; later upstream revisions' `antialiasing` switch) ----
+ * Every projected splat is dilated by 0.3 px^2 (a = c00 + 0.3, b = c01, c = c11 + 0.3 from the EWA
+ * covariance c00, c01, c11) and keeps its opacity, so a splat smaller than a pixel is drawn brighter
+ * than it is.  With antialiasing != 0 the opacity is scaled by the Mip-Splatting 2D filter
+ * normalisation, in fp32, one operation each, no contraction:
+ *     D0 = c00 c11 - c01 c01;  D = a c - b b;  r = D0 / D;  s = sqrtf(fmaxf(0.000025f, r));  op' = op s
+ * op' takes the opacity's place in the splat record and in the culling limit (a splat with
+ * op' < 1/255 gets no instances, as a faint splat does); conic, radius, rectangle, radii, depth,
+ * colour, the sorts and the render are unchanged.  The backward recomputes s from the same values:
+ * with g = dL/dop', dL/dop = s g, and gr = r > 0.000025f ? op g / (2 s) : 0 enters the covariance
+ * chain as dL/dc00 += gr (c11 D - D0 c) / D^2, dL/dc11 += gr (c00 D - D0 a) / D^2,
+ * dL/dc01 += gr (-2 c01 (D - D0)) / D^2, ahead of the cov3D, mean, scale / rotation and camera terms.
+ *
+ * Each entry takes the arguments of the entry it extends plus `antialiasing`, and with
+ * antialiasing == 0 it IS that entry: same launches, same bits, same validation order and messages.
+ *   gs_forward_preprocess_aa   gs_forward_preprocess; follow it with gs_forward_render or _render_aux.
+ *   gs_backward_accumulate_aa  gs_backward_accumulate_aux (aux gradients NULL: gs_backward_accumulate)
+ *                              of a view whose forward was antialiased.  opacities is required
+ *                              ("missing required input pointer"); shs_rest non-NULL is refused
+ *                              (whole SH rows only).  The per-Gaussian kernel is the register-row one
+ *                              at every degree.
+ *   gs_backward_camera_aa      gs_backward_camera behind a gs_backward_accumulate_aa; opacities required.
+ * The forward and the backward of one view must agree on the flag: the gradient is otherwise that of
+ * another function.  The K-view preprocess, the bounded forwards, gs_backward_gaussians and the fused
+ * backward + Adam have no antialiased form. */
+int gs_forward_preprocess_aa(int P, int D, int M, const float* background, int image_width, int image_height,
+                             const float* means3D, const float* shs, const float* colors_precomp,
+                             const float* opacities, const float* scales, float scale_modifier,
+                             const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                             const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                             int prefiltered, int* radii_out, void* geom_buffer, long long* num_rendered_host,
+                             int debug, void* stream, int antialiasing);
+int gs_backward_accumulate_aa(int P, int D, int M, const float* background, int image_width, int image_height,
+                              const float* means3D, const float* shs, const float* shs_rest,
+                              const float* colors_precomp, const float* opacities, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* viewmatrix, const float* projmatrix, const float* campos,
+                              float tan_fovx, float tan_fovy, const int* radii, const void* geom_buffer,
+                              long long num_rendered, const void* binning_buffer, const void* image_buffer,
+                              const float* dL_dout_color, const float* dL_dout_invdepth,
+                              const float* dL_dout_alpha, void* grad_buffer, float* dL_dmeans2D,
+                              float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
+                              float* dL_dsh, float* dL_dscales, float* dL_drotations, unsigned accumulate,
+                              void* wait_event, int debug, void* stream, int antialiasing);
+int gs_backward_camera_aa(int P, int D, int M, const float* background, int image_width, int image_height,
+                          const float* means3D, const float* shs, const float* colors_precomp,
+                          const float* opacities, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                          const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                          const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
+                          int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
+                          float* dL_dcampos, int debug, void* stream, int antialiasing);
 
 /* ---- split SH rows (ABI v8, an extension beyond upstream) ----
  * render() concatenates GaussianModel's features_dc [P,1,3] and features_rest [P,M-1,3] into shs
