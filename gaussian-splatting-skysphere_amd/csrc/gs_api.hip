@@ -1362,6 +1362,41 @@ int gs_backward_render_aux(int P, int D, int M, const float* background, int W, 
   return t_failed ? 1 : 0;
 }
 
+size_t gs_contrib_scratch_bytes(long long num_rendered) {
+  return contrib_scratch_bytes((size_t)(num_rendered > 0 ? num_rendered : 0));
+}
+
+int gs_contrib_stats(int P, int W, int H, const float* viewmatrix, const float* projmatrix, const float* campos,
+                     float tan_fovx, float tan_fovy, const int* radii, const void* geom_buffer,
+                     long long num_rendered, const void* binning_buffer, void* image_buffer,
+                     const float* pixel_weights, void* scratch, float* wsum, float* wmax, int* count,
+                     int accumulate, int debug, void* stream) {
+  (void)radii;
+  clear_error(debug);
+  if (P < 0) return set_error("P must be >= 0"), 1;
+  if (W <= 0 || H <= 0) return set_error("image size must be positive (got %d x %d)", W, H), 1;
+  if (size_limit_error(W, H)) return 1;
+  if (!wsum && !wmax && !count) return set_error("missing output pointer"), 1;
+  if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
+  if (P == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (num_rendered == 0) {  // no instance: zero statistics (nothing to add when accumulating)
+    if (accumulate) return 0;
+    const size_t bytes = sizeof(float) * (size_t)P;
+    if ((wsum && !check_hip(hipMemsetAsync(wsum, 0, bytes, st), "hipMemsetAsync")) ||
+        (wmax && !check_hip(hipMemsetAsync(wmax, 0, bytes, st), "hipMemsetAsync")) ||
+        (count && !check_hip(hipMemsetAsync(count, 0, bytes, st), "hipMemsetAsync")))
+      return 1;
+    return 0;
+  }
+  if (!geom_buffer || !binning_buffer || !image_buffer || !scratch) return set_error("missing buffer pointer"), 1;
+  const CameraArgs c = make_camera(nullptr, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
+  const Layouts L(P, num_rendered, c, geom_buffer, binning_buffer, image_buffer);
+  contrib_stats(P, c, L.geo, L.bin, L.img, pixel_weights, scratch, wsum, wmax, count, accumulate != 0, st);
+  if (!t_failed && check_order_flags(false)) return 1;
+  return t_failed ? 1 : 0;
+}
+
 // scene, grads: the whole scene and the caller's gradient pointers (P rows), of which [first, first + count) run
 static int backward_gaussians_impl(const GaussianArgs& scene, int first, int count, int num_views,
                                    const gs_view_grad* views, const GradOut& grads, void* wait_event, int debug,

@@ -402,14 +402,21 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_tile_order(const uint32_t* __
   }
 }
 
+// (also launched by the contribution statistics, gs_contrib.hip, before or after the view's backward:
+// a pure function of the forward's outputs, so running it again rewrites the same words)
+void bwd_tile_order(const CameraArgs& c, const BinPtrs& bin, const ImgPtrs& img, hipStream_t st) {
+  const uint32_t slots = (uint32_t)(c.gx * c.gy);
+  GS_LAUNCH("tile_order", k_tile_order, dim3((slots + ORDER_THREADS - 1) / ORDER_THREADS), dim3(ORDER_THREADS), 0, st,
+            img.len_hist, img.tile_brank, (uint32_t)c.gx, (uint32_t)c.gy, img.tile_order, img.tile_max, img.ranges,
+            bin.point_list, img.tile_cut, img.cut_max);
+}
+
 void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
                 const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux) {
   const int tiles = c.gx * c.gy;
   uint32_t* order = img.tile_order;
   const uint32_t slots = (uint32_t)tiles;
-  GS_LAUNCH("tile_order", k_tile_order, dim3((slots + ORDER_THREADS - 1) / ORDER_THREADS), dim3(ORDER_THREADS), 0, st,
-            img.len_hist, img.tile_brank, (uint32_t)c.gx, (uint32_t)c.gy, order, img.tile_max, img.ranges,
-            bin.point_list, img.tile_cut, img.cut_max);
+  bwd_tile_order(c, bin, img, st);
 #define GS_BWDTW(NAME, EXACT, AUX)                                                                           \
   GS_LAUNCH(NAME, (k_render_bwd_tw<EXACT, AUX>), dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list, \
             bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, gradrec, aux)

@@ -511,6 +511,16 @@ inline size_t grad_layout_aux(size_t R, size_t P, size_t* o_rec_aux, size_t* o_g
 }
 void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
                 const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux = BwdAux());
+// the backward's launch order and record cuts (tile_order, tile_cut, cut_max) from the forward's
+// outputs; bwd_render launches it itself
+void bwd_tile_order(const CameraArgs& c, const BinPtrs& bin, const ImgPtrs& img, hipStream_t st);
+// ---- per-Gaussian contribution statistics of a rendered view (gs_contrib.hip, gs_contrib_stats) ----
+// scratch: one 12-B record (wsum, wmax, count) per instance slot
+inline size_t contrib_scratch_bytes(size_t I) { return align_up((I ? I : 1) * 12); }
+// weights: [H, W] or null (1); wsum / wmax / count: [P], any may be null; needs instances (I > 0)
+void contrib_stats(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
+                   const float* weights, void* scratch, float* wsum, float* wmax, int* count, bool accumulate,
+                   hipStream_t st);
 struct GradOut {
   float* dmean2D;   // [P, 3]
   float* dcolor;    // [P, 3] or null

@@ -434,6 +434,58 @@ def rasterize_gaussians_aa(background, means3D, colors, opacity, scales, rotatio
                            prefiltered, debug, aux=bool(aux), antialiasing=True)
 
 
+def rasterize_gaussians_two_call(background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                                 cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
+                                 sh, degree, campos, prefiltered, debug, sh_rest=None, antialiasing=False):
+    """rasterize_gaussians, always as the two-call forward over ctypes (gs_forward_preprocess, _split or
+    _aa, then gs_forward_render): the forward contribution_stats is defined for.  Same six values and
+    the same bits as rasterize_gaussians / rasterize_gaussians_aa."""
+    x = _Inputs(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
+                campos, sh_rest=sh_rest)
+    return _forward_ctypes(x, int(image_height), int(image_width), degree, scale_modifier, tan_fovx, tan_fovy,
+                           prefiltered, debug, antialiasing=bool(antialiasing))
+
+
+def contribution_stats(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, campos, tan_fovx,
+                       tan_fovy, image_height, image_width, debug=False, pixel_weights=None, out=None):
+    """Per-Gaussian contribution statistics of one rendered view (gs_contrib_stats, include/gsrast.h):
+    (wsum [P] fp32, wmax [P] fp32, count [P] int32) from the buffers of a two-call forward
+    (rasterize_gaussians_two_call / _aux / _aa), before or after that view's backward.
+    pixel_weights: an [H, W] fp32 device map m >= 0 (None: 1); a pixel of weight 0 adds nothing.
+    out: (wsum, wmax, count) to combine with in place (sum, max, sum); they are returned."""
+    _dev_check(radii, "radii")
+    dev = radii.device
+    P, H, W = int(radii.numel()), int(image_height), int(image_width)
+    if out is None:
+        # every row is written by the kernels (P == 0 or no instance: zero-filled by the library)
+        stats = (torch.empty((P,), dtype=torch.float32, device=dev), torch.empty((P,), dtype=torch.float32, device=dev),
+                 torch.empty((P,), dtype=torch.int32, device=dev))
+    else:
+        stats = tuple(out)
+        for t, dt, n in zip(stats, (torch.float32, torch.float32, torch.int32), ("wsum", "wmax", "count")):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() != P:
+                raise RuntimeError(f"contribution_stats: out {n} must be a contiguous {dt} tensor of {P} elements "
+                                   f"on {dev}")
+    if P == 0:
+        return stats
+    m = None
+    if pixel_weights is not None:
+        m = _f32(pixel_weights, "pixel_weights", dev, allow_empty=False)
+        if m.numel() != H * W:
+            raise RuntimeError("pixel_weights must have shape (H, W)")
+    _, view, proj, cam = _camera_side(dev, None, viewmatrix, projmatrix, campos)
+    R = binning_layout_count(R, binningBuffer, W, H)
+    with torch.cuda.device(dev):
+        scratch = torch.empty((_lib.gs_contrib_scratch_bytes(R),), dtype=torch.uint8, device=dev)
+        _native.check(
+            _lib.gs_contrib_stats(P, W, H, _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx), float(tan_fovy),
+                                  _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer),
+                                  _ptr(m), _ptr(scratch), *map(_ptr, stats), int(out is not None), int(bool(debug)),
+                                  _stream(dev)),
+            "contribution_stats")
+    return stats
+
+
 def binning_layout_count(R, binningBuffer, W, H):
     """The instance count binningBuffer is laid out for, which the C-ABI calls take as num_rendered:
     R for a buffer of gs_binning_buffer_bytes(R) bytes (the two-call, bounded and prepared

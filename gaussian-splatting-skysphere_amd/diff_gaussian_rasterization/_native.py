@@ -191,6 +191,13 @@ SIGNATURES = {
         [_c_i, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
          _c_f, _c_f, _c_p, _c_ll, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p, _c_i],
     ),
+    # GSRAST_HAS_CONTRIB: per-Gaussian contribution statistics (wsum, wmax, count) of a rendered view
+    "gs_contrib_scratch_bytes": (_c_sz, [_c_ll]),
+    "gs_contrib_stats": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_i, _c_i, _c_p],
+    ),
     # GSRAST_HAS_SKY: the skysphere background and its gradients
     "gs_sky_scratch_bytes": (_c_sz, [_c_i, _c_i]),
     "gs_sky_compose_forward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),

@@ -85,6 +85,10 @@ extern "C" {
  * gs_forward_preprocess_aa, gs_backward_accumulate_aa, gs_backward_camera_aa. */
 #define GSRAST_HAS_ANTIALIASING 1
 
+/* Per-Gaussian contribution statistics of a rendered view (additive, same ABI version):
+ * gs_contrib_scratch_bytes, gs_contrib_stats. */
+#define GSRAST_HAS_CONTRIB 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -116,6 +120,8 @@ size_t gs_grad_buffer_bytes_aux(long long num_rendered, int P);
 /* Scratch of gs_backward_camera: one row of 28 doubles (the 27 sums and a zero) per 256 Gaussians,
  * 224 * max(1, ceil(P / 256)) bytes. */
 size_t gs_camera_grad_scratch_bytes(int P);
+/* Scratch of gs_contrib_stats: one 12-byte record per instance slot (rounded up to 256 bytes). */
+size_t gs_contrib_scratch_bytes(long long num_rendered);
 /* The instance count a binning buffer of `bytes` bytes is laid out for: the largest n with
  * gs_binning_buffer_bytes(n, W, H) <= bytes (every such n gives the same layout).  A buffer that
  * gs_forward_counted filled for `capacity` instances goes to the backward with this count in place
@@ -387,6 +393,43 @@ int gs_backward_camera(int P, int D, int M, const float* background, int image_w
                        const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
                        int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
                        float* dL_dcampos, int debug, void* stream);
+
+/* ---- contribution statistics (GSRAST_HAS_CONTRIB, an extension beyond upstream) ----
+ * How much each Gaussian takes part in one rendered view.  For Gaussian i and pixel p, "composited"
+ * means what the colour forward of the same numerics mode decided: the entry's index in the tile's
+ * list is below n_contrib[p], alpha = min(0.99, o G) >= 1/255, and in the exact mode power <= 0.
+ * The entry that stops a pixel (T (1 - alpha) < 1e-4) is not composited, as upstream.
+ * w_i(p) = alpha_i(p) T_i(p), one fp32 product; alpha and T are the floats of the colour walk of
+ * that mode, and the T recurrence is the forward's own: T (1 - alpha) in the exact mode,
+ * fma(-alpha, T, T) in the fast mode.  pixel_weights is an optional map m [H, W], fp32, m >= 0; NULL
+ * means 1.  Three outputs of P entries each (any may be NULL, not all three):
+ *     wsum[i]  = sum_p m_p w_i(p)                                            fp32
+ *     wmax[i]  = max_p m_p w_i(p), 0 if the Gaussian is never composited     fp32
+ *     count[i] = number of pixels where i is composited and m_p != 0         int32
+ * A pixel with m_p = 0 adds nothing to any of the three.  Gaussians with radii == 0 get 0, 0, 0; a
+ * view whose forward recorded an invalid instance list gives zeros, as the backward's record sums do.
+ * Per (tile, Gaussian) instance the walk sums its at most 256 terms in fp32 in a fixed order; a
+ * Gaussian's instances are summed in fp64 in slot order and rounded once.  No float atomics: the
+ * results are bitwise reproducible.
+ *
+ * Call it after gs_forward_render or gs_forward_render_aux of a two-call forward (gs_forward_preprocess,
+ * _split or _aa; an antialiased view's compensated opacity is already in its splat records), before or
+ * after that view's backward: it leaves every word the backward reads as the backward itself would
+ * write it.  It is not defined for the bounded forwards (gs_forward_bounded, gs_forward_counted,
+ * gs_forward_render_bounded) nor for views prepared by gs_forward_preprocess_views / gs_forward_bin_views.
+ * scratch >= gs_contrib_scratch_bytes(num_rendered), 4-byte aligned, the caller's until the kernels
+ * have run.  accumulate != 0 combines with what the outputs hold: wsum = old + new (one fp32 add),
+ * wmax = max(old, new), count = old + new; otherwise all P entries are written.  Checked before any
+ * device work, in this order: P >= 0, a positive image size within the limits above, at least one
+ * output ("missing output pointer"), num_rendered in range, and for P > 0 and num_rendered > 0 the
+ * three buffers and the scratch ("missing buffer pointer").  P == 0 or num_rendered == 0 launches no
+ * walk: the outputs are zero-filled, or left alone when accumulating.  The camera arguments and radii
+ * keep the argument order of gs_backward_render; the kernels read the view's buffers only. */
+int gs_contrib_stats(int P, int image_width, int image_height, const float* viewmatrix, const float* projmatrix,
+                     const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                     const void* geom_buffer, long long num_rendered, const void* binning_buffer,
+                     void* image_buffer, const float* pixel_weights, void* scratch, float* wsum, float* wmax,
+                     int* count, int accumulate, int debug, void* stream);
 
 /* ---- antialiasing (GSRAST_HAS_ANTIALIASING; later upstream revisions' `antialiasing` switch) ----
  * Every projected splat is dilated by 0.3 px^2 (a = c00 + 0.3, b = c01, c = c11 + 0.3 from the EWA
