@@ -1397,6 +1397,71 @@ int gs_contrib_stats(int P, int W, int H, const float* viewmatrix, const float* 
   return t_failed ? 1 : 0;
 }
 
+int gs_feature_group_channels(void) { return GS_FEATURE_GROUP; }
+
+size_t gs_feature_scratch_bytes(long long num_rendered) {
+  return feature_scratch_bytes((size_t)(num_rendered > 0 ? num_rendered : 0));
+}
+
+// the checks the two feature entries share, in the header's order (before any device work)
+static bool feature_args_error(int P, int C, int W, int H, long long num_rendered) {
+  if (P < 0) return set_error("P must be >= 0"), true;
+  if (C < 1 || C > GS_MAX_FEATURE_CHANNELS)
+    return set_error("feature channels must lie in [1, %d] (got %d)", GS_MAX_FEATURE_CHANNELS, C), true;
+  if (W <= 0 || H <= 0) return set_error("image size must be positive (got %d x %d)", W, H), true;
+  if (size_limit_error(W, H)) return true;
+  if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), true;
+  return false;
+}
+
+int gs_feature_forward(int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                       const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                       const void* geom_buffer, long long num_rendered, const void* binning_buffer,
+                       void* image_buffer, const float* features, float* out, int debug, void* stream) {
+  (void)radii;
+  clear_error(debug);
+  if (feature_args_error(P, C, W, H, num_rendered)) return 1;
+  if (!out) return set_error("missing output pointer"), 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (P == 0 || num_rendered == 0)  // no instance: a zero image
+    return check_hip(hipMemsetAsync(out, 0, sizeof(float) * (size_t)C * (size_t)W * (size_t)H, st), "hipMemsetAsync")
+               ? 0
+               : 1;
+  if (!geom_buffer || !binning_buffer || !image_buffer || !features) return set_error("missing buffer pointer"), 1;
+  const CameraArgs c = make_camera(nullptr, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
+  const Layouts L(P, num_rendered, c, geom_buffer, binning_buffer, image_buffer);
+  feature_forward(P, C, c, L.geo, L.bin, L.img, features, out, st);
+  if (!t_failed && check_order_flags(false)) return 1;
+  return t_failed ? 1 : 0;
+}
+
+int gs_feature_backward(int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                        const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                        const void* geom_buffer, long long num_rendered, const void* binning_buffer,
+                        void* image_buffer, const float* dL_dout, void* scratch, float* dL_dfeatures,
+                        int accumulate, int debug, void* stream) {
+  (void)radii;
+  clear_error(debug);
+  if (feature_args_error(P, C, W, H, num_rendered)) return 1;
+  if (P == 0) return 0;
+  if (!dL_dfeatures) return set_error("missing output pointer"), 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (num_rendered == 0) {  // no instance: zero gradients (nothing to add when accumulating)
+    if (accumulate) return 0;
+    return check_hip(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)P * (size_t)C, st), "hipMemsetAsync")
+               ? 0
+               : 1;
+  }
+  if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dout || !scratch)
+    return set_error("missing buffer pointer"), 1;
+  if ((uintptr_t)scratch & 15u) return set_error("scratch must be 16-byte aligned"), 1;
+  const CameraArgs c = make_camera(nullptr, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0);
+  const Layouts L(P, num_rendered, c, geom_buffer, binning_buffer, image_buffer);
+  feature_backward(P, C, c, L.geo, L.bin, L.img, dL_dout, scratch, dL_dfeatures, accumulate != 0, st);
+  if (!t_failed && check_order_flags(false)) return 1;
+  return t_failed ? 1 : 0;
+}
+
 // scene, grads: the whole scene and the caller's gradient pointers (P rows), of which [first, first + count) run
 static int backward_gaussians_impl(const GaussianArgs& scene, int first, int count, int num_views,
                                    const gs_view_grad* views, const GradOut& grads, void* wait_event, int debug,

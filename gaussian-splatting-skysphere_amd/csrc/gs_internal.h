@@ -521,6 +521,17 @@ inline size_t contrib_scratch_bytes(size_t I) { return align_up((I ? I : 1) * 12
 void contrib_stats(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
                    const float* weights, void* scratch, float* wsum, float* wmax, int* count, bool accumulate,
                    hipStream_t st);
+// ---- per-Gaussian feature channels through a rendered view's lists (gs_features.hip) ----
+// channels per walk (gs_feature_group_channels): 4 slots x 8 accumulators per lane
+constexpr int GS_FEATURE_GROUP = 8;
+// scratch of the backward: one record of GS_FEATURE_GROUP floats per instance slot, reused by the groups
+inline size_t feature_scratch_bytes(size_t I) { return align_up((I ? I : 1) * 4 * GS_FEATURE_GROUP); }
+// features [P, C] -> out [C, H, W]; needs instances (I > 0)
+void feature_forward(int P, int C, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
+                     const float* features, float* out, hipStream_t st);
+// dL_dout [C, H, W] -> dL_dfeatures [P, C] (written, or added to); scratch 16-byte aligned; needs instances
+void feature_backward(int P, int C, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
+                      const float* dL_dout, void* scratch, float* dL_dfeatures, bool accumulate, hipStream_t st);
 struct GradOut {
   float* dmean2D;   // [P, 3]
   float* dcolor;    // [P, 3] or null

@@ -486,6 +486,81 @@ def contribution_stats(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmat
     return stats
 
 
+def feature_group_channels():
+    """Channels one walk of the lists carries (gs_feature_group_channels)."""
+    return int(_lib.gs_feature_group_channels())
+
+
+def _feature_matrix(t, name, P, dev):
+    """[P, C] (features) as a contiguous fp32 device tensor; C >= 1 (the library refuses a C beyond its limit)"""
+    if t.ndimension() != 2 or t.size(0) != P or t.size(1) < 1:
+        raise RuntimeError(f"{name} must have shape ({P}, C) with C >= 1 (got {tuple(t.shape)})")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
+    if t.device != dev:
+        _dev_check(t, name)
+        raise RuntimeError(f"{name} is on {t.device}, expected {dev}")
+    return t.contiguous()
+
+
+def feature_forward(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, campos, tan_fovx,
+                    tan_fovy, image_height, image_width, features, debug=False, out=None):
+    """features [P, C] fp32 composited through one rendered view's tile lists (gs_feature_forward,
+    include/gsrast.h): out [C, H, W] = sum_i f_i[c] alpha_i T_i, each channel in the form and order of
+    a colour channel, no background term.  The buffers are those of a two-call forward
+    (rasterize_gaussians_two_call / _aux / _aa), before or after that view's backward.
+    out: a contiguous fp32 [C, H, W] device tensor to write into (every element is written)."""
+    _dev_check(radii, "radii")
+    dev = radii.device
+    P, H, W = int(radii.numel()), int(image_height), int(image_width)
+    f = _feature_matrix(features, "features", P, dev)
+    C = int(f.size(1))
+    if out is None:
+        out = torch.empty((C, H, W), dtype=torch.float32, device=dev)  # every pixel is written by the library
+    elif out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or tuple(out.shape) != (C, H, W):
+        raise RuntimeError(f"feature_forward: out must be a contiguous float32 tensor of shape ({C}, {H}, {W}) on {dev}")
+    _, view, proj, cam = _camera_side(dev, None, viewmatrix, projmatrix, campos)
+    R = binning_layout_count(R, binningBuffer, W, H) if P > 0 else 0
+    with torch.cuda.device(dev):
+        _native.check(
+            _lib.gs_feature_forward(P, C, W, H, _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx), float(tan_fovy),
+                                    _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer),
+                                    _ptr(f), _ptr(out), int(bool(debug)), _stream(dev)),
+            "feature_forward")
+    return out
+
+
+def feature_backward(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmatrix, projmatrix, campos, tan_fovx,
+                     tan_fovy, image_height, image_width, dL_dout, debug=False, out=None):
+    """The gradient of feature_forward in the features (gs_feature_backward): dL_dout [C, H, W] fp32 ->
+    dL_dfeatures [P, C] = sum_p alpha_i T_i dL_dout[c, p], contribution_stats' wsum per channel.
+    out: a contiguous fp32 [P, C] device tensor to ADD to in place (one fp32 add per element); it is returned."""
+    _dev_check(radii, "radii")
+    dev = radii.device
+    P, H, W = int(radii.numel()), int(image_height), int(image_width)
+    if dL_dout.ndimension() != 3 or dL_dout.size(0) < 1 or tuple(dL_dout.shape[1:]) != (H, W):
+        raise RuntimeError(f"dL_dout must have shape (C, {H}, {W}) with C >= 1 (got {tuple(dL_dout.shape)})")
+    g = _f32(dL_dout, "dL_dout", dev, allow_empty=False)
+    C = int(g.size(0))
+    if out is None:
+        grad = torch.empty((P, C), dtype=torch.float32, device=dev)  # every row is written by the library
+    else:
+        grad = out
+        if grad.dtype != torch.float32 or grad.device != dev or not grad.is_contiguous() or tuple(grad.shape) != (P, C):
+            raise RuntimeError(f"feature_backward: out must be a contiguous float32 tensor of shape ({P}, {C}) on {dev}")
+    _, view, proj, cam = _camera_side(dev, None, viewmatrix, projmatrix, campos)
+    R = binning_layout_count(R, binningBuffer, W, H) if P > 0 else 0
+    with torch.cuda.device(dev):
+        scratch = torch.empty((_lib.gs_feature_scratch_bytes(R),), dtype=torch.uint8, device=dev)
+        _native.check(
+            _lib.gs_feature_backward(P, C, W, H, _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx), float(tan_fovy),
+                                     _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer),
+                                     _ptr(g), _ptr(scratch), _ptr(grad), int(out is not None), int(bool(debug)),
+                                     _stream(dev)),
+            "feature_backward")
+    return grad
+
+
 def binning_layout_count(R, binningBuffer, W, H):
     """The instance count binningBuffer is laid out for, which the C-ABI calls take as num_rendered:
     R for a buffer of gs_binning_buffer_bytes(R) bytes (the two-call, bounded and prepared

@@ -198,6 +198,18 @@ SIGNATURES = {
         [_c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
          _c_i, _c_i, _c_p],
     ),
+    # GSRAST_HAS_FEATURES: per-Gaussian feature channels through a rendered view's lists, and their gradient
+    "gs_feature_group_channels": (_c_i, []),
+    "gs_feature_scratch_bytes": (_c_sz, [_c_ll]),
+    "gs_feature_forward": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p],
+    ),
+    "gs_feature_backward": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i,
+         _c_i, _c_p],
+    ),
     # GSRAST_HAS_SKY: the skysphere background and its gradients
     "gs_sky_scratch_bytes": (_c_sz, [_c_i, _c_i]),
     "gs_sky_compose_forward": (_c_i, [_c_i, _c_i, _c_p, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),

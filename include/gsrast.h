@@ -89,6 +89,11 @@ extern "C" {
  * gs_contrib_scratch_bytes, gs_contrib_stats. */
 #define GSRAST_HAS_CONTRIB 1
 
+/* Per-Gaussian feature channels rendered through a view's tile lists, and their gradient (additive,
+ * same ABI version): gs_feature_group_channels, gs_feature_scratch_bytes, gs_feature_forward,
+ * gs_feature_backward. */
+#define GSRAST_HAS_FEATURES 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -122,6 +127,9 @@ size_t gs_grad_buffer_bytes_aux(long long num_rendered, int P);
 size_t gs_camera_grad_scratch_bytes(int P);
 /* Scratch of gs_contrib_stats: one 12-byte record per instance slot (rounded up to 256 bytes). */
 size_t gs_contrib_scratch_bytes(long long num_rendered);
+/* Scratch of gs_feature_backward: one record of gs_feature_group_channels() floats per instance slot
+ * (rounded up to 256 bytes), reused by the channel groups in stream order. */
+size_t gs_feature_scratch_bytes(long long num_rendered);
 /* The instance count a binning buffer of `bytes` bytes is laid out for: the largest n with
  * gs_binning_buffer_bytes(n, W, H) <= bytes (every such n gives the same layout).  A buffer that
  * gs_forward_counted filled for `capacity` instances goes to the backward with this count in place
@@ -430,6 +438,56 @@ int gs_contrib_stats(int P, int image_width, int image_height, const float* view
                      const void* geom_buffer, long long num_rendered, const void* binning_buffer,
                      void* image_buffer, const float* pixel_weights, void* scratch, float* wsum, float* wmax,
                      int* count, int accumulate, int debug, void* stream);
+
+/* ---- feature rendering (GSRAST_HAS_FEATURES, an extension beyond upstream) ----
+ * Any per-Gaussian quantity as an image: features [P, C] (fp32, row-major) composited through the
+ * finished tile lists of one rendered view.  "Composited", alpha_i(p), T_i(p), w_i(p) = alpha_i(p)
+ * T_i(p) and the T recurrence are those of gs_contrib_stats above, for the current numerics mode.
+ *     forward    out[c, p] = sum_i f_i[c] alpha_i(p) T_i(p)              out [C, H, W]
+ *     backward   dL/df_i[c] = sum_p w_i(p) dL_dout[c, p]                 dL_dfeatures [P, C]
+ * The forward composites every channel in the form and order of a colour channel: acc + (f alpha) T
+ * in the exact mode, fma(f, alpha T, acc) in the fast mode, in list order; there is no background
+ * term (compose out + (1 - alpha) bg with the aux alpha) and f is not clamped.  A channel holding a
+ * view's colours therefore reproduces its image over a zero background bit for bit, and a channel of
+ * 1 / depth its aux inverse depth.  Features must be finite.  Every pixel of out is written.
+ * The backward is gs_contrib_stats' wsum with the weight map replaced by channel c of the gradient,
+ * of either sign: per (tile, Gaussian) instance a lane adds its four pixels' terms g_c w (one fp32
+ * product each) in slot order, the 64 lanes are summed in a fixed tree, a Gaussian's instances are
+ * summed in fp64 in slot order and rounded once.  No float atomics: both directions are bitwise
+ * reproducible.  The geometry is constant: neither entry differentiates alpha or T, and nothing flows
+ * to means, scales, rotations or opacities.
+ *
+ * Channels are processed gs_feature_group_channels() at a time (one walk of the lists per group, the
+ * last group padded with zero features whose channels are not written); any 1 <= C <=
+ * GS_MAX_FEATURE_CHANNELS runs, a larger C is refused (render it in slices of columns).
+ *
+ * Call them after gs_forward_render or gs_forward_render_aux of a two-call forward (gs_forward_preprocess,
+ * _split or _aa; an antialiased view's compensated opacity is already in its splat records), before or
+ * after that view's backward: they leave every word the backward reads as the backward itself would
+ * write it.  They are not defined for the bounded forwards (gs_forward_bounded, gs_forward_counted,
+ * gs_forward_render_bounded) nor for views prepared by gs_forward_preprocess_views / gs_forward_bin_views.
+ * A view whose forward recorded an invalid instance list gives zeros in both directions.  Gaussians
+ * with radii == 0 get zero gradient rows.  One view may be rendered any number of times, with any C.
+ * scratch >= gs_feature_scratch_bytes(num_rendered), 16-byte aligned, the caller's until the kernels
+ * have run.  accumulate != 0 adds to what dL_dfeatures holds (one fp32 old + new per element);
+ * otherwise all P rows are written.  Checked before any device work, in this order: P >= 0, C within
+ * [1, GS_MAX_FEATURE_CHANNELS], a positive image size within the limits above, num_rendered in range,
+ * the output ("missing output pointer"; dL_dfeatures only for P > 0), and for P > 0 and num_rendered > 0 the three buffers, the
+ * input and the scratch ("missing buffer pointer").  P == 0 or num_rendered == 0 launches no walk: out
+ * is zero-filled; dL_dfeatures is zero-filled, or left alone when accumulating.  The camera arguments
+ * and radii keep the argument order of gs_backward_render; the kernels read the view's buffers only. */
+#define GS_MAX_FEATURE_CHANNELS 1024
+int gs_feature_group_channels(void);
+int gs_feature_forward(int P, int C, int image_width, int image_height, const float* viewmatrix,
+                       const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                       const int* radii, const void* geom_buffer, long long num_rendered,
+                       const void* binning_buffer, void* image_buffer, const float* features, float* out,
+                       int debug, void* stream);
+int gs_feature_backward(int P, int C, int image_width, int image_height, const float* viewmatrix,
+                        const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                        const int* radii, const void* geom_buffer, long long num_rendered,
+                        const void* binning_buffer, void* image_buffer, const float* dL_dout, void* scratch,
+                        float* dL_dfeatures, int accumulate, int debug, void* stream);
 
 /* ---- antialiasing (GSRAST_HAS_ANTIALIASING; later upstream revisions' `antialiasing` switch) ----
  * Every projected splat is dilated by 0.3 px^2 (a = c00 + 0.3, b = c01, c = c11 + 0.3 from the EWA
