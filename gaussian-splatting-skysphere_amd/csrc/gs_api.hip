@@ -344,6 +344,9 @@ size_t gs_grad_buffer_bytes(long long num_rendered) {
 size_t gs_grad_buffer_bytes_aux(long long num_rendered, int P) {
   return grad_layout_aux((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)(P > 0 ? P : 1), nullptr, nullptr);
 }
+size_t gs_grad_buffer_bytes_absgrad(long long num_rendered, int P) {
+  return grad_layout_abs((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)(P > 0 ? P : 1), nullptr, nullptr);
+}
 
 // Pinned, device-mapped host words: kernels store into them directly (vector stores through the
 // device pointer), so a readback costs no copy launch.
@@ -1085,6 +1088,7 @@ struct BwdIn {
   const float* dL_dout_invdepth = nullptr;  // gs_backward_accumulate_aux (either may be null)
   const float* dL_dout_alpha = nullptr;
   bool antialiasing = false;  // gs_backward_accumulate_aa: the forward scaled the opacities (needs g.opacities)
+  float* dL_dmeans2D_abs = nullptr;  // gs_backward_accumulate_absgrad: [P, 3], or null (the call without it)
 };
 
 // out: the caller's gradient pointers as passed; the ones the scene's inputs cannot receive are dropped here
@@ -1114,7 +1118,15 @@ static int backward_impl(const GaussianArgs& g, const CameraArgs& c, const BwdIn
     aux.gradrec_aux = (float*)((char*)in.grad_buffer + o_rec);
     aux.gsum_aux = (float*)((char*)in.grad_buffer + o_sum);
   }
-  if (num_rendered > 0) bwd_render(P, c, L.geo, L.bin, L.img, in.dL_dout_color, gradrec, st, aux);
+  // the absolute screen-space sums (gs_backward_accumulate_absgrad): their side arrays behind the aux layout
+  BwdAbs ab;
+  if (in.dL_dmeans2D_abs) {
+    size_t o_rec = 0, o_sum = 0;
+    grad_layout_abs((size_t)(num_rendered > 0 ? num_rendered : 1), (size_t)P, &o_rec, &o_sum);
+    ab.gradrec_abs = (float*)((char*)in.grad_buffer + o_rec);
+    ab.gsum_abs = (float*)((char*)in.grad_buffer + o_sum);
+  }
+  if (num_rendered > 0) bwd_render(P, c, L.geo, L.bin, L.img, in.dL_dout_color, gradrec, st, aux, ab);
   // dL_dcov3D is filled whenever the caller passes it: upstream writes it for scale/rotation
   // inputs too (the covariance gradient the scale / rotation chain starts from)
   if (!g.shs) out.dsh = nullptr;
@@ -1122,7 +1134,9 @@ static int backward_impl(const GaussianArgs& g, const CameraArgs& c, const BwdIn
   // the gradient outputs may be shared with views on other streams: order only this last kernel
   if (wait_event && !check_hip(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0), "hipStreamWaitEvent")) return 1;
   bwd_preprocess(g, c, L.geo, L.bin, L.img, gradrec, (uint32_t)num_rendered, num_rendered > 0, out, st, aux,
-                 in.antialiasing);
+                 in.antialiasing, ab);
+  // (without instances no Gaussian has a tile: zero rows, the sums are not read)
+  if (ab.on()) bwd_absgrad(P, c, L.geo, ab, in.dL_dmeans2D_abs, st);
   if (aux.on() && num_rendered > 0) {
     // the depth chain's term, added after the kernel that wrote dL_dmeans3D (same stream, behind the wait)
     bwd_depth_chain(g, c, L.geo, aux, out.dmean3D, st);
@@ -1210,6 +1224,36 @@ int gs_backward_accumulate_aa(int P, int D, int M, const float* background, int 
   BwdIn in{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dout_invdepth,
            dL_dout_alpha};
   in.antialiasing = antialiasing != 0;
+  return backward_impl(
+      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
+                 cov3D_precomp),
+      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0), in,
+      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+              accumulate},
+      wait_event, debug, (hipStream_t)stream);
+}
+
+int gs_backward_accumulate_absgrad(int P, int D, int M, const float* background, int W, int H, const float* means3D,
+                                   const float* shs, const float* shs_rest, const float* colors_precomp,
+                                   const float* opacities, const float* scales, float scale_modifier,
+                                   const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                   const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                   const int* radii, const void* geom_buffer, long long num_rendered,
+                                   const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                                   const float* dL_dout_invdepth, const float* dL_dout_alpha, void* grad_buffer,
+                                   float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
+                                   float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                                   unsigned accumulate, void* wait_event, int debug, void* stream, int antialiasing,
+                                   float* dL_dmeans2D_abs) {
+  (void)radii;
+  if (antialiasing && shs_rest) {
+    clear_error(debug);
+    return set_error("antialiasing: not supported with split SH rows (shs_rest)"), 1;
+  }
+  BwdIn in{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dout_invdepth,
+           dL_dout_alpha};
+  in.antialiasing = antialiasing != 0;
+  in.dL_dmeans2D_abs = dL_dmeans2D_abs;
   return backward_impl(
       make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
                  cov3D_precomp),

@@ -70,7 +70,12 @@ struct BwdSlot {
 // AUX (gs_backward_accumulate_aux): the inverse depth is one more colour channel, of colour 1 / z
 // (br.w) and pixel gradient gD: Cd gains (1 / z) gD and s[9] sums dch gD = dL/d(1 / z).  (Alpha, a
 // channel of colour 0 and background -1, only changes U's start.)
-template <bool EXACT, bool AUX = false>
+// ABS (gs_backward_accumulate_absgrad): two more sums, the absolute screen-space gradient's terms
+// |q| |2A dx + B dy| and |q| |B dx + 2C dy| behind the other sums (A, B, C the staged falloff
+// coefficients: 2A dx + B dy = -log2(e) (cxx dx + cxy dy), so the sums are log2(e) times
+// sum |q (conic . d)|; k_mean2d_absgrad takes the constant out).  The true dx, dy, not the moment
+// offsets; a non-contributing pixel has q = 0 and adds 0.
+template <bool EXACT, bool AUX = false, bool ABS = false>
 __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, const float4 xr, const float4 co,
                                          const float4 br, uint32_t e, float* s) {
   const float bl = br.x;
@@ -109,6 +114,13 @@ __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, c
   s[7] = __builtin_fmaf(qy, my, s[7]);
   s[8] = s[8] + qq;
   if constexpr (AUX) s[9] = __builtin_fmaf(dch, q.gD, s[9]);
+  if constexpr (ABS) {
+    constexpr int A0 = AUX ? GRAD_REC + 1 : GRAD_REC;
+    const float hx = __builtin_fmaf(co.x + co.x, dx, co.y * dy);
+    const float hy = __builtin_fmaf(co.z + co.z, dy, co.y * dx);
+    s[A0] = __builtin_fmaf(__builtin_fabsf(qq), __builtin_fabsf(hx), s[A0]);
+    s[A0 + 1] = __builtin_fmaf(__builtin_fabsf(qq), __builtin_fabsf(hy), s[A0 + 1]);
+  }
   q.T = Tn;
   q.U = __builtin_fmaf(Cd, dch, q.U);
   // the lanes where this slot contributes, from the compares' own lane masks (a ballot of their
@@ -118,7 +130,9 @@ __device__ __forceinline__ uint64_t bwd_slot(BwdSlot& q, float pfx, float pfy, c
   return m;
 }
 
-template <bool EXACT, bool AUX = false>
+// ABS: the kernel takes one more argument, the BwdAbs side arrays (the pack `abs`; empty otherwise, so
+// the other instantiations keep the argument list -- and the code -- they had).
+template <bool EXACT, bool AUX = false, bool ABS = false, class... Abs>
 __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2* __restrict__ ranges,
                                                                     const uint32_t* __restrict__ point_list,
                                                                     const uint32_t* __restrict__ point_gid,
@@ -128,15 +142,20 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
                                                                     const uint32_t* __restrict__ tile_max,
                                                                     const uint32_t* __restrict__ tile_order,
                                                                     const float* __restrict__ dL_dpix,
-                                                                    float* __restrict__ gradrec, BwdAux aux) {
+                                                                    float* __restrict__ gradrec, BwdAux aux,
+                                                                    Abs... abs) {
+  static_assert(sizeof...(Abs) == (ABS ? 1 : 0), "ABS: one BwdAbs argument");
   __shared__ float4 s_xy[64];  // (x, y, r, g)
   __shared__ float4 s_co[64];  // falloff coefficients + opacity (fall_coefs)
   __shared__ float4 s_br[64];  // (b, mean - r: x, y, -), r the moments' reference point (bwd_slot)
   // entry rows of 16 floats (a stride of 20, which puts the flush's 16-B row reads on distinct
   // banks, measured 343 -> 361 us at C3)
   // (AUX: eight more floats, the partials of s9)
-  constexpr int ROW = AUX ? 24 : 16;
-  constexpr int NS = AUX ? GRAD_REC + 1 : GRAD_REC;  // per-entry sums
+  // (ABS: eight more, the partials of the two absolute sums, at AOFF; 32 would put every row on the
+  // same banks, so AUX + ABS pads to 36)
+  constexpr int AOFF = AUX ? 24 : 16;
+  constexpr int ROW = ABS ? (AUX ? 36 : 24) : AOFF;
+  constexpr int NS = GRAD_REC + (AUX ? 1 : 0) + (ABS ? 2 : 0);  // per-entry sums
   __shared__ __attribute__((aligned(16))) float s_acc[64][ROW];
   GS_BWD_T0();
   const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_order ? tile_order[blockIdx.x] : blockIdx.x);
@@ -214,6 +233,10 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
       r[1] = Rec3{a.w, b.x, b.y};
       r[2] = Rec3{b.z, b.w, d.x};
       if constexpr (AUX) aux.gradrec_aux[__float_as_uint(d.y)] = d.z;
+      if constexpr (ABS) {
+        const float4 ea = row[3];  // (words 12, 13: the instance's two absolute sums)
+        reinterpret_cast<float2*>((abs, ...).gradrec_abs)[__float_as_uint(d.y)] = make_float2(ea.x, ea.y);
+      }
     }
   };
   for (uint32_t base = 0; base < n_eff; base += 64) {
@@ -274,12 +297,15 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
 #pragma unroll
       for (int k = 0; k < 4; k++)
         if ((M[k] >> j) & 1ull)
-          con |= bwd_slot<EXACT, AUX>(p[k], pfx0 + (float)(8 * (k & 1)), pfy0 + (float)(8 * (k >> 1)), xr, co, br, e, s);
+          con |= bwd_slot<EXACT, AUX, ABS>(p[k], pfx0 + (float)(8 * (k & 1)), pfy0 + (float)(8 * (k >> 1)), xr, co, br, e, s);
       if (con != 0) {
         wrote |= 1ull << j;
         float d, d8;
-        [[maybe_unused]] float d9;
-        if constexpr (AUX) {
+        [[maybe_unused]] float d9, da;
+        if constexpr (ABS) {
+          wave_sums_abs_halfrows<AUX>(s, hi8, d, d8, d9, da);
+          asm volatile("" ::"v"(d), "v"(d8), "v"(d9), "v"(da));
+        } else if constexpr (AUX) {
           wave_sum10_halfrows(s, hi8, d, d8, d9);
           asm volatile("" ::"v"(d), "v"(d8), "v"(d9));
         } else {
@@ -293,6 +319,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
           acc[0] = d;
           acc[8] = d8;
           if constexpr (AUX) acc[16] = d9;
+          if constexpr (ABS) acc[AOFF] = da;
         }
       }
     }
@@ -312,6 +339,14 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
           const float4 a4 = *reinterpret_cast<const float4*>(&s_acc[lane][16]);
           const float4 a5 = *reinterpret_cast<const float4*>(&s_acc[lane][20]);
           S[9] = ((a4.x + a4.y) + (a4.z + a4.w)) + ((a5.x + a5.y) + (a5.z + a5.w));
+        }
+        if constexpr (ABS) {
+          // the writer lanes 16 r + 8 h store at r + 4 h: words 0, 4, 1, 5 hold the first sum's group
+          // partials (lanes 0-31 of the swapped pair), words 2, 6, 3, 7 the second's
+          const float4 b0 = *reinterpret_cast<const float4*>(&s_acc[lane][AOFF]);
+          const float4 b1 = *reinterpret_cast<const float4*>(&s_acc[lane][AOFF + 4]);
+          S[NS - 2] = (b0.x + b1.x) + (b0.y + b1.y);
+          S[NS - 1] = (b0.z + b1.z) + (b0.w + b1.w);
         }
       } else {
 #pragma unroll
@@ -339,6 +374,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_tw(CameraArgs c, const uint2*
       float s9 = 0.0f;
       if constexpr (AUX) s9 = S[9];
       row[2] = make_float4(S[8] != 0.0f ? S[8] / cop : 0.0f, __uint_as_float(slot), s9, 0.0f);
+      if constexpr (ABS) row[3] = make_float4(S[NS - 2], S[NS - 1], 0.0f, 0.0f);
     }
     rec_lanes = cnt;
     __builtin_amdgcn_wave_barrier();  // the next batch overwrites the staged entries
@@ -412,7 +448,7 @@ void bwd_tile_order(const CameraArgs& c, const BinPtrs& bin, const ImgPtrs& img,
 }
 
 void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
-                const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux) {
+                const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux, const BwdAbs& ab) {
   const int tiles = c.gx * c.gy;
   uint32_t* order = img.tile_order;
   const uint32_t slots = (uint32_t)tiles;
@@ -420,7 +456,22 @@ void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& 
 #define GS_BWDTW(NAME, EXACT, AUX)                                                                           \
   GS_LAUNCH(NAME, (k_render_bwd_tw<EXACT, AUX>), dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list, \
             bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, gradrec, aux)
-  if (aux.on()) {  // an aux gradient: the AUX walk (gs_backward_accumulate_aux)
+#define GS_BWDTW_ABS(NAME, EXACT, AUX)                                                                         \
+  GS_LAUNCH(NAME, (k_render_bwd_tw<EXACT, AUX, true, BwdAbs>), dim3(slots), dim3(64), 0, st, c, img.ranges,       \
+            bin.point_list, bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, \
+            gradrec, aux, ab)
+  if (ab.on()) {  // the absolute screen-space sums too (gs_backward_accumulate_absgrad)
+    if (aux.on()) {
+      if (exact_exp())
+        GS_BWDTW_ABS("render_bwd_aux_abs", true, true);
+      else
+        GS_BWDTW_ABS("render_bwd_aux_abs", false, true);
+    } else if (exact_exp()) {
+      GS_BWDTW_ABS("render_bwd_abs", true, false);
+    } else {
+      GS_BWDTW_ABS("render_bwd_abs", false, false);
+    }
+  } else if (aux.on()) {  // an aux gradient: the AUX walk (gs_backward_accumulate_aux)
     if (exact_exp())
       GS_BWDTW("render_bwd_aux", true, true);
     else
@@ -431,6 +482,7 @@ void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& 
     GS_BWDTW("render_bwd", false, false);
   }
 #undef GS_BWDTW
+#undef GS_BWDTW_ABS
 }
 
 // ------------------------------------------------------------------------------------------
@@ -458,7 +510,10 @@ __device__ __forceinline__ void seg_scan_step(float* v, uint32_t own1) {
 // AUX (the aux backward): a tenth column, the instance's dL/d(1 / z) from the side array
 // gradrec_aux[slot], summed by the same rule into gsum_aux[gid]; the 9-wide instantiation is the
 // plain backward's.
-template <bool AUX = false>
+// ABS (the absgrad backward): two more columns, the instance's absolute sums from gradrec_abs[2 slot],
+// summed by the same rule into gsum_abs[2 gid]; its arrays arrive as one more argument (the pack `abs`,
+// empty otherwise: the other instantiations keep their argument list).
+template <bool AUX = false, bool ABS = false, class... Abs>
 __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_t* __restrict__ counters,
                                                                    const uint32_t* __restrict__ offsets,
                                                                    const uint32_t* __restrict__ sorted_gid,
@@ -468,8 +523,16 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
                                                                    const float* __restrict__ gradrec,
                                                                    float* __restrict__ gsum, uint32_t P,
                                                                    const float* __restrict__ gradrec_aux,
-                                                                   float* __restrict__ gsum_aux) {
-  constexpr int NC = AUX ? GRAD_REC + 1 : GRAD_REC;
+                                                                   float* __restrict__ gsum_aux, Abs... abs) {
+  static_assert(sizeof...(Abs) == (ABS ? 1 : 0), "ABS: one BwdAbs argument");
+  constexpr int A0 = AUX ? GRAD_REC + 1 : GRAD_REC;  // ABS: its two columns
+  constexpr int NC = A0 + (ABS ? 2 : 0);
+  [[maybe_unused]] const float2* gradrec_abs = nullptr;
+  [[maybe_unused]] float* gsum_abs = nullptr;
+  if constexpr (ABS) {
+    gradrec_abs = reinterpret_cast<const float2*>((abs, ...).gradrec_abs);
+    gsum_abs = (abs, ...).gsum_abs;
+  }
   __shared__ double s_acc[SUMREC_WAVES][64][NC];
   __shared__ unsigned long long s_mark[SUMREC_WAVES];
   const uint32_t V = counters[CNT_V], I = counters[CNT_I];
@@ -480,6 +543,7 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
     if (r0 + lane < P) {
       for (int c = 0; c < GRAD_REC; c++) gsum[(size_t)(r0 + lane) * GRAD_REC + c] = 0.0f;
       if constexpr (AUX) gsum_aux[r0 + lane] = 0.0f;
+      if constexpr (ABS) gsum_abs[2 * (size_t)(r0 + lane)] = gsum_abs[2 * (size_t)(r0 + lane) + 1] = 0.0f;
     }
     return;
   }
@@ -504,6 +568,11 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
     if (h) load_rec(gradrec + (size_t)kk * GRAD_REC, vn);
     if constexpr (AUX)
       if (h) vn[GRAD_REC] = gradrec_aux[kk];
+    if constexpr (ABS)
+      if (h) {
+        const float2 t = gradrec_abs[kk];
+        vn[A0] = t.x, vn[A0 + 1] = t.y;
+      }
     hn = __ballot(h);
   }
   for (uint32_t base = S0; base < S1; base += 64) {
@@ -520,6 +589,11 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
       if (h) load_rec(gradrec + (size_t)kn * GRAD_REC, vn);
       if constexpr (AUX)
         if (h) vn[GRAD_REC] = gradrec_aux[kn];
+      if constexpr (ABS)
+        if (h) {
+          const float2 t = gradrec_abs[kn];
+          vn[A0] = t.x, vn[A0 + 1] = t.y;
+        }
       hn = __ballot(h);
     }
     if (hc == 0) {
@@ -559,6 +633,10 @@ __global__ __launch_bounds__(64 * SUMREC_WAVES) void k_sum_records(const uint32_
 #pragma unroll
     for (int c = 0; c < GRAD_REC; c++) gsum[gid * GRAD_REC + c] = (float)s_acc[wid][lane][c];
     if constexpr (AUX) gsum_aux[gid] = (float)s_acc[wid][lane][GRAD_REC];
+    if constexpr (ABS) {
+      gsum_abs[2 * gid] = (float)s_acc[wid][lane][A0];
+      gsum_abs[2 * gid + 1] = (float)s_acc[wid][lane][A0 + 1];
+    }
   }
 }
 
@@ -595,9 +673,18 @@ void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs&
 }
 
 static void launch_sum_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
-                               float* gradrec, uint32_t R, hipStream_t st, const BwdAux& aux = BwdAux()) {
+                               float* gradrec, uint32_t R, hipStream_t st, const BwdAux& aux = BwdAux(),
+                               const BwdAbs& ab = BwdAbs()) {
   const dim3 grid((g.P + 64 * SUMREC_WAVES - 1) / (64 * SUMREC_WAVES)), block(64 * SUMREC_WAVES);
-  if (aux.on())  // the aux backward: the tenth column from / to its side arrays
+  if (ab.on() && aux.on())  // the absgrad backward: its two columns (and the aux column) from / to the side arrays
+    GS_LAUNCH("sum_records_aux_abs", (k_sum_records<true, true, BwdAbs>), grid, block, 0, st, geo.counters,
+              geo.offsets, geo.sorted_gid, bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P,
+              aux.gradrec_aux, aux.gsum_aux, ab);
+  else if (ab.on())
+    GS_LAUNCH("sum_records_abs", (k_sum_records<false, true, BwdAbs>), grid, block, 0, st, geo.counters, geo.offsets,
+              geo.sorted_gid, bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P,
+              (const float*)nullptr, (float*)nullptr, ab);
+  else if (aux.on())  // the aux backward: the tenth column from / to its side arrays
     GS_LAUNCH("sum_records_aux", k_sum_records<true>, grid, block, 0, st, geo.counters, geo.offsets, geo.sorted_gid,
               bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P, aux.gradrec_aux,
               aux.gsum_aux);
@@ -1609,6 +1696,27 @@ __global__ __launch_bounds__(256) void k_mean2d_grad(int P, const uint32_t* __re
   gput(dmean2D, 3 * i + 2, 0.0f, acc, GS_ACC_MEANS2D);
 }
 
+// The absolute screen-space gradient of one view from its record sums' two absolute columns
+// (gs_backward_accumulate_absgrad): the sums carry log2(e) (bwd_slot), taken out here, then the pixel ->
+// NDC scale of dL/dmeans2D; written, [P, 3], zero rows for Gaussians without instances.
+constexpr float K_LN2 = 0.69314718055994531f;
+__global__ __launch_bounds__(256) void k_mean2d_absgrad(int P, const uint32_t* __restrict__ tiles,
+                                                        const float* __restrict__ gsum_abs, float sx, float sy,
+                                                        float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= P) return;
+  const bool vis = tiles[i] != 0;
+  out[3 * (size_t)i] = vis ? (gsum_abs[2 * (size_t)i] * K_LN2) * sx : 0.0f;
+  out[3 * (size_t)i + 1] = vis ? (gsum_abs[2 * (size_t)i + 1] * K_LN2) * sy : 0.0f;
+  out[3 * (size_t)i + 2] = 0.0f;
+}
+
+void bwd_absgrad(int P, const CameraArgs& c, const GeomPtrs& geo, const BwdAbs& ab, float* out, hipStream_t st) {
+  if (P <= 0) return;
+  GS_LAUNCH("mean2d_absgrad", k_mean2d_absgrad, dim3((P + 255) / 256), dim3(256), 0, st, P, geo.tiles, ab.gsum_abs,
+            (float)(0.5 * c.W), (float)(0.5 * c.H), out);
+}
+
 void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img, float* gradrec,
                  uint32_t R, bool have_records, float* dmean2D, uint32_t acc, hipStream_t st, const BwdAux& aux) {
   if (g.P <= 0) return;
@@ -1620,9 +1728,10 @@ void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin,
 
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
-                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux, bool aa) {
+                    bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux, bool aa,
+                    const BwdAbs& ab) {
   if (g.P <= 0) return;
-  if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st, aux);
+  if (have_records) launch_sum_records(g, geo, bin, img, gradrec, R, st, aux, ab);
   dim3 grid((g.P + 255) / 256), block(256);
   const bool sh = g.colors == nullptr && g.shs != nullptr && out.dsh != nullptr;
   if (aa) {  // whole SH rows or colours (the entry refuses split rows): the register variant at every degree

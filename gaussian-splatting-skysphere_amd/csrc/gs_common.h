@@ -542,6 +542,32 @@ __device__ __forceinline__ void wave_sum10_halfrows(const float* s, bool hi, flo
   d9 = v[2];
 }
 
+// The absgrad backward's sums: the nine (AUX: ten) of the functions above, reduced exactly as there, plus
+// the pair s[A0], s[A0 + 1] (A0 = 9, AUX: 10; non-negative terms).  One permlane32 swap-add halves both at
+// once -- lanes 0-31 then hold the first's pair sums, lanes 32-63 the second's -- and the result is reduced
+// like s[8], down to 8-lane groups: on return groups 0-3 of da hold partials of s[A0], groups 4-7 those of
+// s[A0 + 1] (each four add up to the total).  Fixed order.
+template <bool AUX>
+__device__ __forceinline__ void wave_sums_abs_halfrows(const float* s, bool hi, float& d, float& d8, float& d9,
+                                                       float& da) {
+  constexpr int A0 = AUX ? 10 : 9, N = AUX ? 4 : 3;
+  const float c0 = swap32_add(s[0], s[2]), c1 = swap32_add(s[1], s[3]);
+  const float c2 = swap32_add(s[4], s[6]), c3 = swap32_add(s[5], s[7]);
+  const float a = swap16_add(c0, c1), b = swap16_add(c2, c3);
+  const float keep = hi ? b : a, send = hi ? a : b;
+  float v[4] = {keep + dpp_f<0x128>(send), s[8], swap32_add(s[A0], s[A0 + 1]), AUX ? s[9] : 0.0f};  // row_ror:8
+#pragma unroll
+  for (int k = 0; k < N; k++) v[k] = v[k] + dpp_f<0xB1>(v[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) v[k] = v[k] + dpp_f<0x4E>(v[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) v[k] = v[k] + dpp_f<0x141>(v[k]);
+  d = v[0];
+  d8 = v[1];
+  da = v[2];
+  d9 = v[3];
+}
+
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {

@@ -509,8 +509,29 @@ inline size_t grad_layout_aux(size_t R, size_t P, size_t* o_rec_aux, size_t* o_g
   off += align_up(P * sizeof(float));
   return off;
 }
+// the absolute screen-space sums of the backward (gs_backward_accumulate_absgrad): gradrec_abs[2 R] takes
+// each instance's two sums next to its record, gsum_abs[2 P] the per-Gaussian sums.  Null = the kernels
+// without them.
+struct BwdAbs {
+  float* gradrec_abs = nullptr;
+  float* gsum_abs = nullptr;
+  bool on() const { return gradrec_abs != nullptr; }
+};
+// the grad scratch of the absgrad backward: the aux layout (whether or not an aux gradient is present, so
+// gs_backward_camera finds gsum_aux where it was) | gradrec_abs[2 R] | gsum_abs[2 P]
+inline size_t grad_layout_abs(size_t R, size_t P, size_t* o_rec_abs, size_t* o_gsum_abs) {
+  size_t off = grad_layout_aux(R, P, nullptr, nullptr);
+  if (o_rec_abs) *o_rec_abs = off;
+  off += align_up(2 * R * sizeof(float));
+  if (o_gsum_abs) *o_gsum_abs = off;
+  off += align_up(2 * P * sizeof(float));
+  return off;
+}
 void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
-                const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux = BwdAux());
+                const float* dL_dpix, float* gradrec, hipStream_t st, const BwdAux& aux = BwdAux(),
+                const BwdAbs& ab = BwdAbs());
+// dL_dmeans2D_abs [P, 3] from gsum_abs, after the record sums (k_mean2d_absgrad)
+void bwd_absgrad(int P, const CameraArgs& c, const GeomPtrs& geo, const BwdAbs& ab, float* out, hipStream_t st);
 // the backward's launch order and record cuts (tile_order, tile_cut, cut_max) from the forward's
 // outputs; bwd_render launches it itself
 void bwd_tile_order(const CameraArgs& c, const BinPtrs& bin, const ImgPtrs& img, hipStream_t st);
@@ -575,7 +596,8 @@ void bwd_records(const GaussianArgs& g, const GeomPtrs& geo, const BinPtrs& bin,
 void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin,
                     const ImgPtrs& img, float* gradrec, uint32_t R,
                     bool have_records, const GradOut& out, hipStream_t st, const BwdAux& aux = BwdAux(),
-                    bool aa = false);  // aa: the view's forward was antialiased (g.opacities is read)
+                    bool aa = false,  // aa: the view's forward was antialiased (g.opacities is read)
+                    const BwdAbs& ab = BwdAbs());
 // the aux backward's per-Gaussian tail, after the kernel that writes the gradients: the depth
 // chain's add into dL/dmeans3D (from gsum_aux, summed with the other record sums)
 void bwd_depth_chain(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo, const BwdAux& aux,

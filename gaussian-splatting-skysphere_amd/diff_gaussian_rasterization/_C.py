@@ -584,7 +584,7 @@ GS_ACC = {n: 1 << k for k, n in enumerate(GRAD_NAMES)}
 def backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                   projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                   imageBuffer, debug, want_all=True, sinks=None, wait_event=None, sh_rest=None, aux_grads=None,
-                  camera=None, aa_opacity=None):
+                  camera=None, aa_opacity=None, absgrad=False):
     """Shared backward.  With want_all=False the gradients that no autograd input can receive
     (colours when SHs drive the colour, cov3D when scale/rotation drive it, ...) are None and
     not computed.  sinks: {name: (buffer, accumulate)} -- that gradient is written into (or, with
@@ -600,7 +600,10 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     gs_backward_camera, run right behind the backward on its stream (over ctypes).
     aa_opacity: the opacities [P, 1] of a rasterize_gaussians_aa forward -- the backward of an antialiased
     view (gs_backward_accumulate_aa / gs_backward_camera_aa, over ctypes), which chains through the
-    opacity scale and so reads them; None: a plain forward's backward."""
+    opacity scale and so reads them; None: a plain forward's backward.
+    absgrad: the return ends with one more item (after the camera gradients), the view's absolute
+    screen-space gradient [P, 3] (gs_backward_accumulate_absgrad, over ctypes; with sh_rest, aux_grads,
+    camera and aa_opacity as above)."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None
     antialiasing = aa_opacity is not None
@@ -609,7 +612,7 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     if camera is not None and sh_rest is not None:
         raise RuntimeError("camera_grads: not supported with split SH rows (sh_split=)")
     if (_EXT is not None and not want_all and means3D.is_cuda and aux_grads is None and camera is None
-            and not antialiasing):
+            and not antialiasing and not absgrad):
         return _EXT.backward(background, means3D, radii, colors, scales, rotations, float(scale_modifier),
                              cov3D_precomp, viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color,
                              sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, bool(debug),
@@ -653,6 +656,10 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     if camera is not None:  # written by the finishing kernel, structural zeros included (P == 0: no launch)
         cam_out = (torch.zeros if P == 0 else torch.empty)((35,), **f32)
         ret += ((cam_out[:16].view(4, 4), cam_out[16:32].view(4, 4), cam_out[32:] if camera else None),)
+    abs_out = None
+    if absgrad:  # written by its kernel, zero rows included (P == 0: no launch)
+        abs_out = torch.empty((P, 3), **f32)
+        ret += (abs_out,)
     if P == 0:
         return ret
     dpix = _f32(dL_dout_color, "dL_dout_color", dev)
@@ -670,16 +677,23 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
         tail = (acc, wait, int(bool(debug)), st)
         what = "rasterize_gaussians_backward"
         d_inv = d_alpha = None
+        n_scratch = _lib.gs_grad_buffer_bytes(R)
         if aux_grads is not None:
             d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
             for t in (d_inv, d_alpha):
                 if t is not None and t.numel() != H * W:
                     raise RuntimeError("aux gradients must have shape (1, H, W)")
-            grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes_aux(R, P),), dtype=torch.uint8, device=dev)
+            n_scratch = _lib.gs_grad_buffer_bytes_aux(R, P)
             what += " (aux outputs)"
-        else:
-            grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes(R),), dtype=torch.uint8, device=dev)
-        if antialiasing:
+        if absgrad:
+            n_scratch = _lib.gs_grad_buffer_bytes_absgrad(R, P)
+        grad_scratch = torch.empty((n_scratch,), dtype=torch.uint8, device=dev)
+        if absgrad:
+            rc = _lib.gs_backward_accumulate_absgrad(
+                *head, *x.scene(scale_modifier, None if antialiasing else x.sh_rest, x.colors), *bufs, _ptr(d_inv),
+                _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail, int(antialiasing), _ptr(abs_out))
+            what += " (antialiasing, absgrad)" if antialiasing else " (absgrad)"
+        elif antialiasing:
             rc = _lib.gs_backward_accumulate_aa(*head, *x.scene(scale_modifier, None, x.colors), *bufs, _ptr(d_inv),
                                                 _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail, 1)
             what += " (antialiasing)"

@@ -15,6 +15,8 @@ Public surface used by the reference's render adapter
         -> the same outputs; settings.viewmatrix / .projmatrix / .campos receive gradients
     GaussianRasterizer(raster_settings)(..., antialiasing=True)     (extension; later upstream's switch)
         -> the same outputs, every splat's opacity compensated for the 0.3 px^2 dilation
+    GaussianRasterizer(raster_settings)(..., absgrad=True)          (extension; AbsGS, gsplat's `absgrad`)
+        -> the same outputs; after backward() means2D.absgrad holds sum_p |dL_p/dmean2D| [P, 3]
     GaussianRasterizer.markVisible(positions) -> bool [P]
     rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings)
@@ -132,10 +134,12 @@ class GaussianRasterizationSettings(NamedTuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, prepared=None, sh_split=None, binning_capacity=None, antialiasing=False):
+                        raster_settings, prepared=None, sh_split=None, binning_capacity=None, antialiasing=False,
+                        absgrad=None):
+    """absgrad: None, or the call's _AbsgradHolder (GaussianRasterizer(...)(..., absgrad=True))."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, prepared, sh_split, binning_capacity,
-                                     bool(antialiasing))
+                                     bool(antialiasing), absgrad)
 
 
 # ------------------------------------------------------------------------------------------
@@ -270,18 +274,48 @@ def _antialiasing_refusal(prepared=None, binning_capacity=None, sh_split=None):
             raise RuntimeError(f"antialiasing: not supported with {name}=")
 
 
+# ------------------------------------------------------------------------------------------
+# Absolute screen-space gradients (an extension beyond the upstream API; AbsGS, gsplat's `absgrad`).
+# absgrad=True: the backward's tile walk also sums |dL_p/dmean2D| over each splat's pixels (the signed sum
+# in means2D.grad cancels for a large splat over fine detail, which then never crosses the densification
+# threshold), and the caller's means2D tensor gets `.absgrad`, [P, 3] fp32 in the units of means2D.grad,
+# written (not accumulated) by that backward.  The other outputs and gradients are bit-identical to the
+# call without it.  The backward goes over ctypes (gs_backward_accumulate_absgrad).  Prepared views,
+# bounded forwards and deferring gradient owners are refused: the K-view / bounded forwards are those of
+# the multi-view and graph-captured steps, which do not densify per view through this call, and a
+# deferring owner's per-tile half (gs_backward_render) has no absolute sums.
+# ------------------------------------------------------------------------------------------
+class _AbsgradHolder:
+    """Carries the caller's means2D tensor to the backward (autograd hands the Function's inputs back
+    as other tensor objects; a non-tensor argument passes through as it is)."""
+
+    def __init__(self, means2D):
+        self.tensor = means2D
+
+
+def _absgrad_refusal(prepared=None, binning_capacity=None):
+    for name, v in (("prepared", prepared), ("binning_capacity", binning_capacity)):
+        if v is not None:
+            raise RuntimeError(f"absgrad: not supported with {name}=")
+
+
+_T_ABS_DEFER = ("absgrad: not supported with a deferring gradient owner (GradBucket(defer=True), the fused "
+                "backward + Adam of gs_train_step)")
+
 _T_AA_DEFER = ("antialiasing: not supported with a deferring gradient owner (GradBucket(defer=True), the fused "
                "backward + Adam of gs_train_step)")
 
 
 def _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s,
-                  prepared=None, sh_split=None, binning_capacity=None, aux=False, antialiasing=False):
+                  prepared=None, sh_split=None, binning_capacity=None, aux=False, antialiasing=False, absgrad=None):
     """The forward of the three autograd Functions: the native call (plain, with split SH rows or a
     binning capacity, over a prepared view, with the aux outputs, or antialiased), everything the
     backward needs on `ctx`, and the call's gradient sinks.  -> (color, radii), or with aux (color,
     radii, invdepth, alpha)."""
     if antialiasing:
         _antialiasing_refusal(prepared, binning_capacity, sh_split)
+    if absgrad is not None:
+        _absgrad_refusal(prepared, binning_capacity)
     # the camera matrices arrive transposed (cameras.py:54-56 world_view_transform is a
     # .transpose(0, 1) view); make them contiguous once and reuse them in backward
     view, proj = _contiguous_matrix(s.viewmatrix), _contiguous_matrix(s.projmatrix)
@@ -324,6 +358,7 @@ def _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     ctx.num_rendered = num_rendered
     ctx.matrices = (view, proj)
     ctx.antialiasing = bool(antialiasing)
+    ctx.absgrad = absgrad  # None, or the holder of the caller's means2D
     ctx.sh_rest = sh_rest
     # the split rows are kept outside save_for_backward (they are not inputs of the Function):
     # their version counters stand in for autograd's in-place check
@@ -360,7 +395,11 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
     owner, camera gradients) refuse it first."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None  # only the colour reached the loss (or nothing did): the plain backward
+    absgrad = getattr(ctx, "absgrad", None)
     if grad_out_color is None and aux_grads is None:  # no output reached the loss
+        if absgrad is not None:
+            t = absgrad.tensor
+            t.absgrad = torch.zeros((t.shape[0], 3), dtype=torch.float32, device=ctx.saved_tensors[1].device)
         return (None,) * 8, None
     s = ctx.raster_settings
     colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = (
@@ -380,6 +419,8 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
     # when every parameter gradient the call needs goes to it: only the per-tile half and
     # dL_dmeans2D run now, the per-Gaussian half later for all of its views in one pass
     deferrer = _deferring_owner(ctx)
+    if deferrer is not None and absgrad is not None:
+        raise RuntimeError(_T_ABS_DEFER)  # its per-tile half (gs_backward_render) has no absolute sums
     if deferrer is not None and antialiasing:
         # its per-Gaussian half (k_backward_gaussians, the fused backward + Adam) has no opacity-scale chain
         raise RuntimeError(_T_AA_DEFER)
@@ -422,13 +463,15 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
             st.wait_event(e)
         wait = evs[0] if evs else None
 
+    more = {} if absgrad is None else {"absgrad": True}  # (the default call's arguments are what they were)
+
     def _bwd(*a):
         return _C.backward_impl(*a, want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
-                                aux_grads=aux_grads, camera=camera)
+                                aux_grads=aux_grads, camera=camera, **more)
 
     def _bwd_aa(*a):  # (the snapshot's arguments end with the flag and the opacities)
         return _C.backward_impl(*a[:-2], want_all=False, sinks=sinks, wait_event=wait, sh_rest=ctx.sh_rest,
-                                aux_grads=aux_grads, camera=camera, aa_opacity=a[-1])
+                                aux_grads=aux_grads, camera=camera, aa_opacity=a[-1], **more)
 
     if antialiasing:
         res = _run_with_snapshot(_bwd_aa, args + (True, ctx.saved_tensors[10]), s.debug, "snapshot_bw.dump",
@@ -437,6 +480,8 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
         res = _run_with_snapshot(_bwd, args, s.debug, "snapshot_bw.dump", "backward")
     (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
      grad_rotations) = res[:8]
+    if absgrad is not None:
+        absgrad.tensor.absgrad = res[-1]  # written by this backward (a second one writes the same bits)
     for o in owners:
         if hasattr(o, "written"):
             o.written(st)
@@ -450,13 +495,15 @@ def _backward_step(ctx, grad_out_color, aux_grads=None, camera=None):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, prepared=None, sh_split=None, binning_capacity=None, antialiasing=False):
+                raster_settings, prepared=None, sh_split=None, binning_capacity=None, antialiasing=False,
+                absgrad=None):
         return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, prepared, sh_split, binning_capacity, antialiasing=antialiasing)
+                             raster_settings, prepared, sh_split, binning_capacity, antialiasing=antialiasing,
+                             absgrad=absgrad)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
-        return _backward_step(ctx, grad_out_color)[0] + (None,) * 5
+        return _backward_step(ctx, grad_out_color)[0] + (None,) * 6
 
 
 # ------------------------------------------------------------------------------------------
@@ -471,18 +518,18 @@ class _RasterizeGaussians(torch.autograd.Function):
 # bounded forwards and deferring gradient owners that do not opt in (owner.accepts_aux) are refused.
 # ------------------------------------------------------------------------------------------
 def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                            raster_settings, sh_split=None, antialiasing=False):
+                            raster_settings, sh_split=None, antialiasing=False, absgrad=None):
     """-> (color, radii, invdepth, alpha)"""
     return _RasterizeGaussiansAux.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                        cov3Ds_precomp, raster_settings, sh_split, bool(antialiasing))
+                                        cov3Ds_precomp, raster_settings, sh_split, bool(antialiasing), absgrad)
 
 
 class _RasterizeGaussiansAux(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, sh_split=None, antialiasing=False):
+                raster_settings, sh_split=None, antialiasing=False, absgrad=None):
         return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, sh_split=sh_split, aux=True, antialiasing=antialiasing)
+                             raster_settings, sh_split=sh_split, aux=True, antialiasing=antialiasing, absgrad=absgrad)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_invdepth, grad_alpha):
@@ -493,7 +540,7 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                 and not getattr(deferrer, "accepts_aux", False)):
             raise RuntimeError("aux_outputs: an alpha / inverse-depth gradient is not supported with a deferring "
                                "gradient owner (GradBucket(defer=True), the fused backward + Adam of gs_train_step)")
-        return _backward_step(ctx, grad_out_color, (grad_invdepth, grad_alpha))[0] + (None, None, None)
+        return _backward_step(ctx, grad_out_color, (grad_invdepth, grad_alpha))[0] + (None,) * 4
 
 
 # ------------------------------------------------------------------------------------------
@@ -509,12 +556,12 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
 class _RasterizeGaussiansCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                viewmatrix, projmatrix, campos, raster_settings, aux, antialiasing=False):
+                viewmatrix, projmatrix, campos, raster_settings, aux, antialiasing=False, absgrad=None):
         # (viewmatrix, projmatrix, campos are raster_settings' own tensors: inputs for the graph's sake)
         ctx.camera_aux = aux
         ctx.camera_meta = tuple((t.shape, t.device) for t in (viewmatrix, projmatrix, campos))
         return _forward_step(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, aux=aux, antialiasing=antialiasing)
+                             raster_settings, aux=aux, antialiasing=antialiasing, absgrad=absgrad)
 
     @staticmethod
     def backward(ctx, *grad_outs):
@@ -529,7 +576,7 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 shape, device = ctx.camera_meta[k]
                 if g is not None and ctx.needs_input_grad[8 + k]:
                     cam[k] = g.reshape(shape).to(device)
-        return grads + tuple(cam) + (None, None, None)
+        return grads + tuple(cam) + (None,) * 4
 
 
 def _deferring_owner(ctx):
@@ -559,7 +606,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, prepared=None, sh_split=None, binning_capacity=None, aux_outputs=False,
-                camera_grads=False, antialiasing=False):
+                camera_grads=False, absgrad=False, antialiasing=False):
         """prepared: this call's PreparedView from prepare_views (extension; default: none).
         binning_capacity: size the binning buffer for that many instances and run the forward
         without a host wait (extension, ABI v10; see bounded_status()).
@@ -578,11 +625,23 @@ class GaussianRasterizer(nn.Module):
         `antialiasing` switch, the Mip-Splatting 2D filter normalisation), so a splat smaller than a
         pixel keeps its energy at any resolution; gradients chain through the scale (extension; with
         or without aux_outputs / camera_grads; not with prepared=, binning_capacity=, sh_split= or a
-        deferring gradient owner).  False: today's kernels and bits."""
+        deferring gradient owner).  False: today's kernels and bits.
+        absgrad: after backward(), the caller's means2D tensor carries `.absgrad` [P, 3] fp32: the sum
+        over each splat's pixels of the absolute per-pixel screen-space gradient, in the units of
+        means2D.grad[:, :2] (column 2 is 0), written by that backward -- what AbsGS densifies on, since
+        the signed sum cancels for a large splat over detail (extension; with or without sh_split=,
+        aux_outputs, camera_grads, antialiasing; means2D must require grad; not with prepared=,
+        binning_capacity= or a deferring gradient owner).  False: today's calls and bits."""
         s = self.raster_settings
         antialiasing = bool(antialiasing)
         if antialiasing:
             _antialiasing_refusal(prepared, binning_capacity, sh_split)
+        holder = None
+        if absgrad:
+            _absgrad_refusal(prepared, binning_capacity)
+            if not (isinstance(means2D, torch.Tensor) and means2D.requires_grad):
+                raise RuntimeError("absgrad: means2D does not require grad")
+            holder = _AbsgradHolder(means2D)
         if camera_grads:
             for name, v in (("prepared", prepared), ("binning_capacity", binning_capacity), ("sh_split", sh_split)):
                 if v is not None:
@@ -608,9 +667,9 @@ class GaussianRasterizer(nn.Module):
         if camera_grads:
             return _RasterizeGaussiansCamera.apply(means3D, means2D, shs, colors_precomp, opacities, scales,
                                                    rotations, cov3D_precomp, s.viewmatrix, s.projmatrix, s.campos, s,
-                                                   bool(aux_outputs), antialiasing)
+                                                   bool(aux_outputs), antialiasing, holder)
         if aux_outputs:
             return rasterize_gaussians_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                           cov3D_precomp, s, sh_split, antialiasing)
+                                           cov3D_precomp, s, sh_split, antialiasing, holder)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   s, prepared, sh_split, binning_capacity, antialiasing)
+                                   s, prepared, sh_split, binning_capacity, antialiasing, holder)

@@ -191,6 +191,14 @@ SIGNATURES = {
         [_c_i, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
          _c_f, _c_f, _c_p, _c_ll, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p, _c_i],
     ),
+    # GSRAST_HAS_ABSGRAD: gs_backward_accumulate_aa plus the absolute screen-space gradient output
+    "gs_grad_buffer_bytes_absgrad": (_c_sz, [_c_ll, _c_i]),
+    "gs_backward_accumulate_absgrad": (
+        _c_i,
+        [_c_i, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_f, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+         _c_p, ctypes.c_uint, _c_p, _c_i, _c_p, _c_i, _c_p],
+    ),
     # GSRAST_HAS_CONTRIB: per-Gaussian contribution statistics (wsum, wmax, count) of a rendered view
     "gs_contrib_scratch_bytes": (_c_sz, [_c_ll]),
     "gs_contrib_stats": (

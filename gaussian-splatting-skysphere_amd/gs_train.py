@@ -371,13 +371,23 @@ def _check_densify_stats(max_radii2D, grad_accum, denom, radii, viewspace_grad) 
         raise TypeError("radii: expected a contiguous int32 device tensor (the rasterizer's output)")
 
 
-def add_densification_stats(gaussians, viewspace_point_tensor: torch.Tensor, radii: torch.Tensor) -> None:
+def add_densification_stats(gaussians, viewspace_point_tensor: torch.Tensor, radii: torch.Tensor,
+                            absgrad: bool = False) -> None:
     """train.py:115-116 in one launch: updates gaussians.max_radii2D, .xyz_gradient_accum, .denom
-    for the visible Gaussians (radii > 0, the reference's visibility_filter)."""
-    if viewspace_point_tensor.grad is None:
-        raise RuntimeError("add_densification_stats: viewspace_point_tensor has no gradient (call backward first)")
-    densify_stats(gaussians.max_radii2D, gaussians.xyz_gradient_accum, gaussians.denom, radii,
-                  viewspace_point_tensor.grad)
+    for the visible Gaussians (radii > 0, the reference's visibility_filter).
+    absgrad: accumulate the norm of viewspace_point_tensor.absgrad, the absolute screen-space gradient of a
+    GaussianRasterizer(...)(..., absgrad=True) call, instead of that of .grad (AbsGS; the same kernel)."""
+    if absgrad:
+        vgrad = getattr(viewspace_point_tensor, "absgrad", None)
+        if vgrad is None:
+            raise RuntimeError("add_densification_stats: viewspace_point_tensor has no .absgrad (render with "
+                               "absgrad=True and call backward first)")
+    else:
+        vgrad = viewspace_point_tensor.grad
+        if vgrad is None:
+            raise RuntimeError("add_densification_stats: viewspace_point_tensor has no gradient (call backward "
+                               "first)")
+    densify_stats(gaussians.max_radii2D, gaussians.xyz_gradient_accum, gaussians.denom, radii, vgrad)
 
 
 def _aligned(t: torch.Tensor) -> torch.Tensor:

@@ -144,7 +144,8 @@ class _AdamBackward:
 
 
 def render(model: TrainModel, settings, fused: bool = True, act_leaves: list | None = None, split_sh: bool = True,
-           binning_capacity: int | None = None, sink_owner=None, row_waits=None, aux_outputs: bool = False):
+           binning_capacity: int | None = None, sink_owner=None, row_waits=None, aux_outputs: bool = False,
+           absgrad: bool = False):
     """gaussian_renderer.render() for the default pipe (SH and covariance in the rasterizer).
     act_leaves (a list): the activated inputs are made autograd leaves (their adjoint then runs in
     FusedAdam.step_activated) and appended to it as (shs, opacity, scales, rotations).
@@ -153,7 +154,8 @@ def render(model: TrainModel, settings, fused: bool = True, act_leaves: list | N
     row_waits (fused=True, the autograd activation; [(lo, hi, event)] from row 0): the parameters'
     rows become ready chunk by chunk on other streams (ShardedAdam's all-gathers of the previous
     step); the activation and the rasterizer's preprocess run chunk by chunk behind them.
-    aux_outputs: the rasterizer's aux call; returns (image, screenspace_points, radii, invdepth, alpha)."""
+    aux_outputs: the rasterizer's aux call; returns (image, screenspace_points, radii, invdepth, alpha).
+    absgrad: the rasterizer's absgrad=True; screenspace_points.absgrad is there after the backward."""
     if row_waits and (act_leaves is not None or not fused):
         raise ValueError("render: row_waits apply to the fused autograd activation only")
     sh_split = None
@@ -192,16 +194,18 @@ def render(model: TrainModel, settings, fused: bool = True, act_leaves: list | N
         out = GaussianRasterizer(raster_settings=settings)(
             means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=opacity,
             scales=scales, rotations=rotations, cov3D_precomp=None, sh_split=sh_split,
-            binning_capacity=binning_capacity, **({"aux_outputs": True} if aux_outputs else {}))
+            binning_capacity=binning_capacity, **({"aux_outputs": True} if aux_outputs else {}),
+            **({"absgrad": True} if absgrad else {}))
     if act_waits:  # (the preprocess waited for every chunk; anything after it on this stream sees all rows)
         torch.cuda.current_stream(means3D.device).wait_event(act_waits[-1][2])
     return (out[0], screenspace_points) + tuple(out[1:])
 
 
-def _torch_densification_stats(model: TrainModel, viewspace, radii):
+def _torch_densification_stats(model: TrainModel, viewspace, radii, absgrad: bool = False):
     vis = radii > 0  # train.py:115-116, gaussian_model.py:405-407
+    vgrad = viewspace.absgrad if absgrad else viewspace.grad
     model.max_radii2D[vis] = torch.max(model.max_radii2D[vis], radii[vis].to(model.max_radii2D.dtype))
-    model.xyz_gradient_accum[vis] += torch.norm(viewspace.grad[vis, :2], dim=-1, keepdim=True)
+    model.xyz_gradient_accum[vis] += torch.norm(vgrad[vis, :2], dim=-1, keepdim=True)
     model.denom[vis] += 1
 
 
@@ -237,7 +241,7 @@ def _bg_is_zero(bg: torch.Tensor) -> bool:
 def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool = True, densify_stats: bool = True,
                lambda_dssim: float = LAMBDA_DSSIM, fused_adjoint: bool = True, split_sh: bool = True,
                loss_item: bool = False, binning_capacity: int | None = None, fuse_adam: bool = False,
-               sky=None, depth_prior: torch.Tensor | None = None, depth_weight: float = 0.0):
+               sky=None, depth_prior: torch.Tensor | None = None, depth_weight: float = 0.0, absgrad: bool = False):
     """One iteration (module docstring).  Returns the loss tensor, or with loss_item=True the
     reference's per-iteration `loss.item()` (train.py:99, its progress-bar EMA): a host read-back
     that waits for the forward and backward, taken where train.py takes it (before the statistics
@@ -265,7 +269,16 @@ def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool 
     Both run the rasterizer's aux call and work on every path above except binning_capacity (the aux
     forward is not bounded): with fuse_adam the alpha / inverse-depth gradients go through the
     deferred aux backward (_AdamBackward.accepts_aux), bit-identical to the unfused step.  An invalid
-    view raises with the texture, its moments and its step count untouched as well."""
+    view raises with the texture, its moments and its step count untouched as well.
+    absgrad: the render runs with the rasterizer's absgrad=True and the densification statistics accumulate
+    the norm of the absolute screen-space gradient (AbsGS) instead of the signed one; parameters, moments
+    and the loss are unaffected, only xyz_gradient_accum is.  With sky= / depth_prior= as well; not with
+    fuse_adam (the fused pass reads the deferred per-tile half, which has no absolute sums) or
+    binning_capacity (the bounded forward's backward is the plain one)."""
+    if absgrad and fuse_adam:
+        raise ValueError("train_step: absgrad= is not supported with fuse_adam=True")
+    if absgrad and binning_capacity is not None:
+        raise ValueError("train_step: absgrad= is not supported with a bounded forward (binning_capacity=)")
     with_depth = depth_prior is not None and depth_weight > 0
     if sky is not None and sky is not False:
         if sky is True:
@@ -293,11 +306,12 @@ def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool 
     try:
         if aux:
             image, viewspace, radii, invdepth, alpha = render(model, settings, fused, acts, split_sh, None, owner,
-                                                              aux_outputs=True)
+                                                              aux_outputs=True, absgrad=absgrad)
             if sky is not None:
                 image = gs_sky.compose(image, alpha, sky.texture, settings)
         else:
-            image, viewspace, radii = render(model, settings, fused, acts, split_sh, binning_capacity, owner)
+            image, viewspace, radii = render(model, settings, fused, acts, split_sh, binning_capacity, owner,
+                                             absgrad=absgrad)
         if fused:  # the whole loss expression in one fused forward / backward (gs_loss.photometric_loss)
             loss, Ll1 = gs_loss.photometric_loss(image, gt_image, lambda_dssim)
         else:
@@ -383,9 +397,9 @@ def train_step(model: TrainModel, settings, gt_image: torch.Tensor, fused: bool 
                 fused_launch()
             elif densify_stats:
                 if fused:
-                    gs_train.add_densification_stats(model, viewspace, radii)
+                    gs_train.add_densification_stats(model, viewspace, radii, absgrad=absgrad)
                 else:
-                    _torch_densification_stats(model, viewspace, radii)
+                    _torch_densification_stats(model, viewspace, radii, absgrad)
             if fused_launch is not None:
                 pass  # (the optimizer step ran above, fused with the per-Gaussian backward)
             elif acts:

@@ -94,6 +94,10 @@ extern "C" {
  * gs_feature_backward. */
 #define GSRAST_HAS_FEATURES 1
 
+/* Absolute screen-space gradients for densification (additive, same ABI version):
+ * gs_grad_buffer_bytes_absgrad, gs_backward_accumulate_absgrad. */
+#define GSRAST_HAS_ABSGRAD 1
+
 int gs_abi_version(void);
 const char* gs_last_error(void);
 
@@ -541,6 +545,44 @@ int gs_backward_camera_aa(int P, int D, int M, const float* background, int imag
                           const void* geom_buffer, long long num_rendered, const void* aux_grad_buffer,
                           int aux_valid, void* scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
                           float* dL_dcampos, int debug, void* stream, int antialiasing);
+
+/* ---- absolute screen-space gradients (GSRAST_HAS_ABSGRAD; AbsGS, gsplat's `absgrad`) ----
+ * dL_dmeans2D is a signed sum over a splat's pixels; a large splat over fine detail is pulled both ways
+ * and the sum cancels.  dL_dmeans2D_abs [P, 3] sums the per-pixel gradient's absolute value instead:
+ * with q = o G dL/dalpha of a composited (pixel, Gaussian) pair (the backward walk's own decisions and
+ * floats; a pair that is not composited adds exactly 0), d = mean2D - pixel and (cxx, cxy, cyy) the conic,
+ *     abs[i][0] = 0.5 W sum_p |q (cxx dx + cxy dy)|,  abs[i][1] = 0.5 H sum_p |q (cxy dx + cyy dy)|,  abs[i][2] = 0
+ * in the units of dL_dmeans2D[:, :2], whose argument is the signed sum of the same terms.  Evaluated as
+ * |q| |2A dx + B dy| and |q| |B dx + 2C dy| with the staged falloff coefficients A = -log2(e) cxx / 2,
+ * B = -log2(e) cxy, C = -log2(e) cyy / 2 (fp32: 2A = A + A, one product, one FMA, one FMA into the sum);
+ * the lane's pixel slots are summed in slot order, the wave in a fixed tree once per tile entry, a
+ * Gaussian's tile records in fp64 in slot order with one rounding, and the result is
+ * (sum * ln 2) * (0.5 W) (resp. 0.5 H), two fp32 products in that order.  No float atomics: bitwise
+ * reproducible.  Written, not accumulated; a Gaussian without instances, P == 0 and a view whose
+ * forward reported an invalid instance list give zeros.
+ *
+ * gs_backward_accumulate_absgrad takes the arguments of gs_backward_accumulate_aa (those of
+ * gs_backward_accumulate_aux plus `antialiasing`; shs_rest as in _aux, both aux gradients may be NULL,
+ * antialiasing != 0 with shs_rest is refused as there) plus dL_dmeans2D_abs.  With aux gradients the
+ * dL/dalpha in q is the aux walk's.  grad_buffer >= gs_grad_buffer_bytes_absgrad(num_rendered, P), which
+ * keeps the layout of gs_grad_buffer_bytes_aux in front: gs_backward_camera (/ _aa) may follow with this
+ * grad_buffer as its aux_grad_buffer, the record sums in the geometry buffer being what they were.
+ * With dL_dmeans2D_abs == NULL it runs exactly gs_backward_accumulate_aa: same launches, same bits (and
+ * the smaller grad_buffer of that call suffices). */
+size_t gs_grad_buffer_bytes_absgrad(long long num_rendered, int P);
+int gs_backward_accumulate_absgrad(int P, int D, int M, const float* background, int image_width, int image_height,
+                                   const float* means3D, const float* shs, const float* shs_rest,
+                                   const float* colors_precomp, const float* opacities, const float* scales,
+                                   float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                   const float* viewmatrix, const float* projmatrix, const float* campos,
+                                   float tan_fovx, float tan_fovy, const int* radii, const void* geom_buffer,
+                                   long long num_rendered, const void* binning_buffer, const void* image_buffer,
+                                   const float* dL_dout_color, const float* dL_dout_invdepth,
+                                   const float* dL_dout_alpha, void* grad_buffer, float* dL_dmeans2D,
+                                   float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
+                                   float* dL_dsh, float* dL_dscales, float* dL_drotations, unsigned accumulate,
+                                   void* wait_event, int debug, void* stream, int antialiasing,
+                                   float* dL_dmeans2D_abs);
 
 /* ---- split SH rows (ABI v8, an extension beyond upstream) ----
  * render() concatenates GaussianModel's features_dc [P,1,3] and features_rest [P,M-1,3] into shs
