@@ -1104,6 +1104,9 @@ static int backward_impl(const GaussianArgs& g, const CameraArgs& c, const BwdIn
   if (!in.geom || !in.binning || !in.image || !in.dL_dout_color || !in.grad_buffer)
     return set_error("missing buffer pointer"), 1;
   if (!out.dmean2D || !out.dopacity || !out.dmean3D) return set_error("missing gradient output pointer"), 1;
+  // SH colours chain into dL/dmeans3D through the view direction inside the kernels that form dL/dsh:
+  // without that output the colours kernel would run and leave the term out
+  if (g.shs && !out.dsh) return set_error("dL_dsh is required with SHs"), 1;
   if (num_rendered < 0 || num_rendered > GS_MAX_INSTANCES) return set_error("num_rendered out of range"), 1;
   if (out.acc & ~0xFFu) return set_error("accumulate: unknown GS_ACC bits 0x%x", out.acc), 1;
   const Layouts L(P, num_rendered, c, in.geom, in.binning, in.image);
@@ -1525,6 +1528,7 @@ static int backward_gaussians_impl(const GaussianArgs& scene, int first, int cou
   if (scene.shs && (scene.D < 0 || scene.D > 3 || scene.M < (scene.D + 1) * (scene.D + 1)))
     return set_error("bad SH degree / coefficient count"), 1;
   if (!grads.dopacity || !grads.dmean3D) return set_error("missing gradient output pointer"), 1;
+  if (scene.shs && !grads.dsh) return set_error("dL_dsh is required with SHs"), 1;  // (as backward_impl)
   if (grads.acc & ~0xFFu) return set_error("accumulate: unknown GS_ACC bits 0x%x", grads.acc), 1;
   for (int v = 0; v < num_views; v++) {
     const gs_view_grad& w = views[v];

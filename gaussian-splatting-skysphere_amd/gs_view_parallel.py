@@ -249,6 +249,11 @@ class GradBucket:
                                    "the deferred backward ran")
             outs[name], accumulate = claim
             acc |= _C.GS_ACC[name] if accumulate else 0
+        sh = inputs["sh"]
+        if "sh" not in outs and sh is not None and sh.numel():
+            # SH colours whose tensor takes no gradient here: the kernels form the view-direction term of
+            # dL/dmeans3D together with dL/dsh (the library refuses SHs without that output); a scratch takes it
+            outs["sh"] = torch.empty(sh.shape, dtype=torch.float32, device=sh.device)
         return inputs, [d[1] for d in self._deferred], outs, acc
 
     def _deferred_pass(self, inputs, views, outs, acc, first=0, count=None):

@@ -316,6 +316,8 @@ long long gs_rasterize_forward(int P, int D, int M, const float* background, int
  * dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
  * dL_dscales[P,3], dL_drotations[P,4].  dL_dcolors, dL_dcov3D, dL_dsh, dL_dscales and
  * dL_drotations may be NULL when the matching input was not given (they are then not computed).
+ * With shs given, dL_dsh is required ("dL_dsh is required with SHs"): the SH colours' dependence on
+ * the view direction is part of dL_dmeans3D and is formed together with dL_dsh.
  * Ref: upstream rasterize_gaussians_backward. */
 int gs_backward(int P, int D, int M, const float* background, int image_width, int image_height,
                 const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
@@ -623,7 +625,9 @@ int gs_backward_accumulate_split(int P, int D, int M, const float* background, i
  *   Arguments as gs_backward.
  * gs_backward_gaussians: views[0 .. num_views) in order (any count: more than 8 run as several
  *   passes); outputs and `accumulate` bits as gs_backward_accumulate (dL_dmeans2D excluded);
- *   wait_event as gs_backward_accumulate. */
+ *   wait_event as gs_backward_accumulate.  As there, SH inputs without a dL_dsh output are refused
+ *   ("dL_dsh is required with SHs") rather than answered with a dL_dmeans3D that lacks the SH
+ *   colours' view-direction term; dL_dcolors, dL_dcov3D, dL_dscales and dL_drotations may be NULL. */
 typedef struct gs_view_grad {
   const float* viewmatrix; /* 16, device (as the forward's) */
   const float* projmatrix; /* 16, device */

@@ -140,6 +140,7 @@ E_CAMPOS = "campos is required with SHs"
 E_OUT = "missing output pointer"
 E_BUF = "missing buffer pointer"
 E_GRAD = "missing gradient output pointer"
+E_DSH = "dL_dsh is required with SHs"
 E_NR = "num_rendered out of range"
 E_CAP = "capacity out of range"
 E_REST = "split SH: features_rest is NULL"
@@ -471,6 +472,33 @@ def build_rows():
          "densify stats: grad_stride must be >= 2", None),
         (e, dict(denom=X, shs=ODD), 1, "split SH rows must be 16-byte aligned", None),
     ]
+    # ---- SH colours need their dL_dsh output (the view-direction term of dL_dmeans3D is formed with it):
+    # ---- checked behind the required gradient pointers, in front of num_rendered / the accumulate bits / the
+    # ---- views; precomputed colours do without.  (Appended here: the ids of the rows above carry their index.)
+    for e in ("gs_backward", "gs_backward_accumulate", "gs_backward_accumulate_aux", "gs_backward_accumulate_split"):
+        rows += [
+            (e, dict(dsh=None), 1, E_DSH, None),
+            (e, dict(dsh=None, num_rendered=-1), 1, E_DSH, None),
+            (e, dict(dsh=None, dmeans3D=None), 1, E_GRAD, None),
+            (e, dict(dsh=None, image=None), 1, E_BUF, None),
+            (e, dict(dsh=None, P=0), 0, "", None),
+        ]
+        if e != "gs_backward_accumulate_split":
+            rows += [(e, dict(COLOURS, dsh=None, dcolors=None, dcov3D=None, num_rendered=-1), 1, E_NR, None)]
+        if e != "gs_backward":
+            rows += [(e, dict(dsh=None, accumulate=0x100), 1, E_DSH, None)]
+    for e in ("gs_backward_gaussians", "gs_backward_gaussians_range"):
+        rows += [
+            (e, dict(dsh=None), 1, E_DSH, None),
+            (e, dict(dsh=None, accumulate=0x100), 1, E_DSH, None),
+            (e, dict(dsh=None, view_list=views(view(image_width=0))), 1, E_DSH, None),
+            (e, dict(dsh=None, dopacity=None), 1, E_GRAD, None),
+            (e, dict(dsh=None, M=9), 1, "bad SH degree / coefficient count", None),
+            (e, dict(dsh=None, num_views=0), 0, "", None),
+            # precomputed colours: no dL_dsh, and neither dL_dcolors, dL_dcov3D, dL_dscales nor dL_drotations is required
+            (e, dict(shs=None, colors=X, D=9, M=0, dsh=None, dcolors=None, dcov3D=None, dscales=None, drots=None,
+                     view_list=views(view(image_width=0))), 1, "view 0: bad image size", None),
+        ]
     return rows
 
 
