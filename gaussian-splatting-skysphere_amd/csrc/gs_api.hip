@@ -1174,15 +1174,12 @@ int gs_backward_accumulate(int P, int D, int M, const float* background, int W, 
                            float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                            float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                            unsigned accumulate, void* wait_event, int debug, void* stream) {
-  (void)radii;
-  return backward_impl(
-      make_scene(P, D, M, means3D, shs, nullptr, colors_precomp, opacities, scales, scale_modifier, rotations,
-                 cov3D_precomp),
-      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
-      BwdIn{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer},
-      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-              accumulate},
-      wait_event, debug, (hipStream_t)stream);
+  return gs_backward_accumulate_absgrad(P, D, M, background, W, H, means3D, shs, nullptr, colors_precomp, opacities,
+                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, num_rendered, binning_buffer,
+                                        image_buffer, dL_dout_color, nullptr, nullptr, grad_buffer, dL_dmeans2D,
+                                        dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+                                        dL_drotations, accumulate, wait_event, debug, stream, 0, nullptr);
 }
 
 int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1196,16 +1193,12 @@ int gs_backward_accumulate_aux(int P, int D, int M, const float* background, int
                                float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                                float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                                unsigned accumulate, void* wait_event, int debug, void* stream) {
-  (void)radii;
-  return backward_impl(
-      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
-                 cov3D_precomp),
-      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
-      BwdIn{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dout_invdepth,
-            dL_dout_alpha},
-      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-              accumulate},
-      wait_event, debug, (hipStream_t)stream);
+  return gs_backward_accumulate_absgrad(P, D, M, background, W, H, means3D, shs, shs_rest, colors_precomp, opacities,
+                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, num_rendered, binning_buffer,
+                                        image_buffer, dL_dout_color, dL_dout_invdepth, dL_dout_alpha, grad_buffer,
+                                        dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                                        dL_dscales, dL_drotations, accumulate, wait_event, debug, stream, 0, nullptr);
 }
 
 int gs_backward_accumulate_aa(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1219,21 +1212,13 @@ int gs_backward_accumulate_aa(int P, int D, int M, const float* background, int 
                               float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                               float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                               unsigned accumulate, void* wait_event, int debug, void* stream, int antialiasing) {
-  (void)radii;
-  if (antialiasing && shs_rest) {
-    clear_error(debug);
-    return set_error("antialiasing: not supported with split SH rows (shs_rest)"), 1;
-  }
-  BwdIn in{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer, dL_dout_invdepth,
-           dL_dout_alpha};
-  in.antialiasing = antialiasing != 0;
-  return backward_impl(
-      make_scene(P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
-                 cov3D_precomp),
-      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0), in,
-      GradOut{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-              accumulate},
-      wait_event, debug, (hipStream_t)stream);
+  return gs_backward_accumulate_absgrad(P, D, M, background, W, H, means3D, shs, shs_rest, colors_precomp, opacities,
+                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, num_rendered, binning_buffer,
+                                        image_buffer, dL_dout_color, dL_dout_invdepth, dL_dout_alpha, grad_buffer,
+                                        dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                                        dL_dscales, dL_drotations, accumulate, wait_event, debug, stream, antialiasing,
+                                        nullptr);
 }
 
 int gs_backward_accumulate_absgrad(int P, int D, int M, const float* background, int W, int H, const float* means3D,
@@ -1276,19 +1261,16 @@ int gs_backward_accumulate_split(int P, int D, int M, const float* background, i
                                  float* dL_dmeans2D, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
                                  float* dL_dsh, float* dL_dscales, float* dL_drotations, unsigned accumulate,
                                  void* wait_event, int debug, void* stream) {
-  (void)radii;
   if (!shs_rest) {
     clear_error(debug);
     return set_error("split SH: features_rest is NULL"), 1;
   }
-  return backward_impl(
-      make_scene(P, D, M, means3D, shs_dc, shs_rest, nullptr, opacities, scales, scale_modifier, rotations,
-                 cov3D_precomp),
-      make_camera(background, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, 0),
-      BwdIn{geom_buffer, num_rendered, binning_buffer, image_buffer, dL_dout_color, grad_buffer},
-      GradOut{dL_dmeans2D, nullptr, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-              accumulate},
-      wait_event, debug, (hipStream_t)stream);
+  return gs_backward_accumulate_absgrad(P, D, M, background, W, H, means3D, shs_dc, shs_rest, nullptr, opacities,
+                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, num_rendered, binning_buffer,
+                                        image_buffer, dL_dout_color, nullptr, nullptr, grad_buffer, dL_dmeans2D,
+                                        nullptr, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+                                        dL_drotations, accumulate, wait_event, debug, stream, 0, nullptr);
 }
 
 size_t gs_camera_grad_scratch_bytes(int P) { return camera_grad_scratch_bytes((size_t)(P > 0 ? P : 0)); }

@@ -453,36 +453,21 @@ void bwd_render(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& 
   uint32_t* order = img.tile_order;
   const uint32_t slots = (uint32_t)tiles;
   bwd_tile_order(c, bin, img, st);
-#define GS_BWDTW(NAME, EXACT, AUX)                                                                           \
-  GS_LAUNCH(NAME, (k_render_bwd_tw<EXACT, AUX>), dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list, \
-            bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, gradrec, aux)
-#define GS_BWDTW_ABS(NAME, EXACT, AUX)                                                                         \
-  GS_LAUNCH(NAME, (k_render_bwd_tw<EXACT, AUX, true, BwdAbs>), dim3(slots), dim3(64), 0, st, c, img.ranges,       \
-            bin.point_list, bin.presort_gid, geo.splat, img.final_T, img.n_contrib, img.tile_max, order, dL_dpix, \
-            gradrec, aux, ab)
-  if (ab.on()) {  // the absolute screen-space sums too (gs_backward_accumulate_absgrad)
-    if (aux.on()) {
-      if (exact_exp())
-        GS_BWDTW_ABS("render_bwd_aux_abs", true, true);
-      else
-        GS_BWDTW_ABS("render_bwd_aux_abs", false, true);
-    } else if (exact_exp()) {
-      GS_BWDTW_ABS("render_bwd_abs", true, false);
-    } else {
-      GS_BWDTW_ABS("render_bwd_abs", false, false);
-    }
-  } else if (aux.on()) {  // an aux gradient: the AUX walk (gs_backward_accumulate_aux)
-    if (exact_exp())
-      GS_BWDTW("render_bwd_aux", true, true);
-    else
-      GS_BWDTW("render_bwd_aux", false, true);
-  } else if (exact_exp()) {
-    GS_BWDTW("render_bwd", true, false);
-  } else {
-    GS_BWDTW("render_bwd", false, false);
-  }
-#undef GS_BWDTW
-#undef GS_BWDTW_ABS
+  // abs: the ABS walk's one more argument, or nothing (the kernel's pack)
+  auto launch = [&](const char* name, const char* name_aux, auto... abs) {
+    with_flag(aux.on(), [&](auto AUX) {  // an aux gradient: the AUX walk (gs_backward_accumulate_aux)
+      with_flag(exact_exp(), [&](auto EXACT) {
+        constexpr bool E = decltype(EXACT)::value, A = decltype(AUX)::value;
+        GS_LAUNCH(A ? name_aux : name, (k_render_bwd_tw<E, A, sizeof...(abs) != 0, decltype(abs)...>), dim3(slots),
+                  dim3(64), 0, st, c, img.ranges, bin.point_list, bin.presort_gid, geo.splat, img.final_T,
+                  img.n_contrib, img.tile_max, order, dL_dpix, gradrec, aux, abs...);
+      });
+    });
+  };
+  if (ab.on())  // the absolute screen-space sums too (gs_backward_accumulate_absgrad)
+    launch("render_bwd_abs", "render_bwd_aux_abs", ab);
+  else
+    launch("render_bwd", "render_bwd_aux");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -676,22 +661,19 @@ static void launch_sum_records(const GaussianArgs& g, const GeomPtrs& geo, const
                                float* gradrec, uint32_t R, hipStream_t st, const BwdAux& aux = BwdAux(),
                                const BwdAbs& ab = BwdAbs()) {
   const dim3 grid((g.P + 64 * SUMREC_WAVES - 1) / (64 * SUMREC_WAVES)), block(64 * SUMREC_WAVES);
-  if (ab.on() && aux.on())  // the absgrad backward: its two columns (and the aux column) from / to the side arrays
-    GS_LAUNCH("sum_records_aux_abs", (k_sum_records<true, true, BwdAbs>), grid, block, 0, st, geo.counters,
-              geo.offsets, geo.sorted_gid, bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P,
-              aux.gradrec_aux, aux.gsum_aux, ab);
-  else if (ab.on())
-    GS_LAUNCH("sum_records_abs", (k_sum_records<false, true, BwdAbs>), grid, block, 0, st, geo.counters, geo.offsets,
-              geo.sorted_gid, bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P,
-              (const float*)nullptr, (float*)nullptr, ab);
-  else if (aux.on())  // the aux backward: the tenth column from / to its side arrays
-    GS_LAUNCH("sum_records_aux", k_sum_records<true>, grid, block, 0, st, geo.counters, geo.offsets, geo.sorted_gid,
-              bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P, aux.gradrec_aux,
-              aux.gsum_aux);
+  // abs: the ABS kernels' one more argument, or nothing (the kernel's pack)
+  auto launch = [&](const char* name, const char* name_aux, auto... abs) {
+    with_flag(aux.on(), [&](auto AUX) {  // the aux backward: the tenth column from / to its side arrays
+      constexpr bool A = decltype(AUX)::value;
+      GS_LAUNCH(A ? name_aux : name, (k_sum_records<A, sizeof...(abs) != 0, decltype(abs)...>), grid, block, 0, st,
+                geo.counters, geo.offsets, geo.sorted_gid, bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum,
+                (uint32_t)g.P, A ? aux.gradrec_aux : (const float*)nullptr, A ? aux.gsum_aux : (float*)nullptr, abs...);
+    });
+  };
+  if (ab.on())  // the absgrad backward: its two columns (and the aux column) from / to the side arrays
+    launch("sum_records_abs", "sum_records_aux_abs", ab);
   else
-    GS_LAUNCH("sum_records", k_sum_records<false>, grid, block, 0, st, geo.counters, geo.offsets, geo.sorted_gid,
-              bin.slot_tile, img.tile_cut, img.cut_max, gradrec, geo.gsum, (uint32_t)g.P, (const float*)nullptr,
-              (float*)nullptr);
+    launch("sum_records", "sum_records_aux");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1428,22 +1410,13 @@ void bwd_gaussians_adam(const GaussianArgs& g, const CameraArgs& c, const GeomPt
                         hipStream_t st) {
   if (g.P <= 0) return;
   const dim3 grid((g.P + 255) / 256), block(256);
-#define GS_PBWD_ADAM(D)                                                                                          \
-  do {                                                                                                          \
-    if (a.invdepth_sums)                                                                                        \
-      GS_LAUNCH("preprocess_bwd_adam_aux", (k_preprocess_bwd_adam<D, true>), grid, block, 0, st, g, c, geo.tiles, \
-                geo.clamped, geo.gsum, a);                                                                      \
-    else                                                                                                        \
-      GS_LAUNCH("preprocess_bwd_adam", (k_preprocess_bwd_adam<D, false>), grid, block, 0, st, g, c, geo.tiles,  \
-                geo.clamped, geo.gsum, a);                                                                      \
-  } while (0)
-  switch (g.D) {
-    case 0: GS_PBWD_ADAM(0); break;
-    case 1: GS_PBWD_ADAM(1); break;
-    case 2: GS_PBWD_ADAM(2); break;
-    default: GS_PBWD_ADAM(3); break;
-  }
-#undef GS_PBWD_ADAM
+  with_degree(g.D, [&](auto D) {
+    with_flag(a.invdepth_sums != nullptr, [&](auto AUX) {
+      GS_LAUNCH(decltype(AUX)::value ? "preprocess_bwd_adam_aux" : "preprocess_bwd_adam",
+                (k_preprocess_bwd_adam<decltype(D)::value, decltype(AUX)::value>), grid, block, 0, st, g, c, geo.tiles,
+                geo.clamped, geo.gsum, a);
+    });
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1670,16 +1643,9 @@ void bwd_gaussians(const GaussianArgs& g, const FusedViews& fv, const GradOut& o
   if (g.P <= 0 || fv.K <= 0) return;
   dim3 grid((g.P + 255) / 256), block(256);
   const bool sh = g.colors == nullptr && g.shs != nullptr && out.dsh != nullptr;
-  if (!sh) {
-    GS_LAUNCH("backward_gaussians", k_backward_gaussians<-1>, grid, block, 0, st, g, fv, out);
-    return;
-  }
-  switch (g.D) {
-    case 0: GS_LAUNCH("backward_gaussians", k_backward_gaussians<0>, grid, block, 0, st, g, fv, out); break;
-    case 1: GS_LAUNCH("backward_gaussians", k_backward_gaussians<1>, grid, block, 0, st, g, fv, out); break;
-    case 2: GS_LAUNCH("backward_gaussians", k_backward_gaussians<2>, grid, block, 0, st, g, fv, out); break;
-    default: GS_LAUNCH("backward_gaussians", k_backward_gaussians<3>, grid, block, 0, st, g, fv, out); break;
-  }
+  with_degree<-1>(sh ? g.D : -1, [&](auto D) {
+    GS_LAUNCH("backward_gaussians", k_backward_gaussians<decltype(D)::value>, grid, block, 0, st, g, fv, out);
+  });
 }
 
 // dL/dmeans2D of one view straight from its record sums (the per-view output of the split
@@ -1735,21 +1701,15 @@ void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& 
   dim3 grid((g.P + 255) / 256), block(256);
   const bool sh = g.colors == nullptr && g.shs != nullptr && out.dsh != nullptr;
   if (aa) {  // whole SH rows or colours (the entry refuses split rows): the register variant at every degree
-#define GS_PBWD_AA(D)                                                                                          \
-  GS_LAUNCH("preprocess_bwd", (k_preprocess_bwd_reg_aa<D>), grid, block, 0, st, g, c, geo.tiles, geo.clamped, \
-            geo.gsum, out)
     if (!sh) {
       GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_colors_aa, grid, block, 0, st, g, c, geo.tiles, geo.clamped,
                 geo.gsum, out);
       return;
     }
-    switch (g.D) {
-      case 0: GS_PBWD_AA(0); break;
-      case 1: GS_PBWD_AA(1); break;
-      case 2: GS_PBWD_AA(2); break;
-      default: GS_PBWD_AA(3); break;
-    }
-#undef GS_PBWD_AA
+    with_degree(g.D, [&](auto D) {
+      GS_LAUNCH("preprocess_bwd", (k_preprocess_bwd_reg_aa<decltype(D)::value>), grid, block, 0, st, g, c, geo.tiles,
+                geo.clamped, geo.gsum, out);
+    });
     return;
   }
   if (!sh) {
@@ -1758,42 +1718,19 @@ void bwd_preprocess(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& 
     return;
   }
   if (sh_stage_ok(g) && (((uintptr_t)out.dsh) & 15) == 0 && !(out.acc & GS_ACC_SH)) {
-    if (g.shs_rest)
-      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_stage<true>, grid, block, 0, st, g, c, geo.tiles, geo.clamped,
-                geo.gsum, out);
-    else
-      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_stage<false>, grid, block, 0, st, g, c, geo.tiles, geo.clamped,
-                geo.gsum, out);
+    with_flag(g.shs_rest != nullptr, [&](auto SPLIT) {
+      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_stage<decltype(SPLIT)::value>, grid, block, 0, st, g, c, geo.tiles,
+                geo.clamped, geo.gsum, out);
+    });
     return;
   }
   // split SH rows are otherwise read by the register variant only
-  if (g.shs_rest) {
-#define GS_PBWD_SPLIT(D)                                                                                        \
-  GS_LAUNCH("preprocess_bwd", (k_preprocess_bwd_reg<D, true>), grid, block, 0, st, g, c, geo.tiles, geo.clamped, \
-            geo.gsum, out)
-    switch (g.D) {
-      case 0: GS_PBWD_SPLIT(0); break;
-      case 1: GS_PBWD_SPLIT(1); break;
-      case 2: GS_PBWD_SPLIT(2); break;
-      default: GS_PBWD_SPLIT(3); break;
-    }
-#undef GS_PBWD_SPLIT
-    return;
-  }
-  switch (g.D) {
-    case 0:
-      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_reg<0>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, out);
-      break;
-    case 1:
-      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_reg<1>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, out);
-      break;
-    case 2:
-      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_reg<2>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, out);
-      break;
-    default:
-      GS_LAUNCH("preprocess_bwd", k_preprocess_bwd_reg<3>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, out);
-      break;
-  }
+  with_degree(g.D, [&](auto D) {
+    with_flag(g.shs_rest != nullptr, [&](auto SPLIT) {
+      GS_LAUNCH("preprocess_bwd", (k_preprocess_bwd_reg<decltype(D)::value, decltype(SPLIT)::value>), grid, block, 0,
+                st, g, c, geo.tiles, geo.clamped, geo.gsum, out);
+    });
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1989,23 +1926,12 @@ void bwd_camera(const GaussianArgs& g, const CameraArgs& c, const GeomPtrs& geo,
   const int nb = (g.P + 255) / 256;
   const dim3 grid(nb), block(256);
   const int deg = (dcampos && g.shs && !g.colors) ? g.D : -1;
-#define GS_CAMG(D)                                                                                                  \
-  do {                                                                                                              \
-    if (aa)                                                                                                         \
-      GS_LAUNCH("camera_grad", (k_camera_grad<D, true>), grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum,      \
-                gsum_aux, geo.splat, partial);                                                                      \
-    else                                                                                                            \
-      GS_LAUNCH("camera_grad", k_camera_grad<D>, grid, block, 0, st, g, c, geo.tiles, geo.clamped, geo.gsum, gsum_aux, \
-                geo.splat, partial);                                                                                \
-  } while (0)
-  switch (deg) {
-    case 0: GS_CAMG(0); break;
-    case 1: GS_CAMG(1); break;
-    case 2: GS_CAMG(2); break;
-    case 3: GS_CAMG(3); break;
-    default: GS_CAMG(-1); break;
-  }
-#undef GS_CAMG
+  with_degree<-1>(deg, [&](auto D) {
+    with_flag(aa, [&](auto AA) {
+      GS_LAUNCH("camera_grad", (k_camera_grad<decltype(D)::value, decltype(AA)::value>), grid, block, 0, st, g, c,
+                geo.tiles, geo.clamped, geo.gsum, gsum_aux, geo.splat, partial);
+    });
+  });
   GS_LAUNCH("camera_grad_finish", k_camera_grad_finish, dim3(1), dim3(CAMG_FINISH_THREADS), 0, st, geo.counters, partial, nb, dview,
             dproj, dcampos);
 }

@@ -348,14 +348,10 @@ void contrib_stats(int P, const CameraArgs& c, const GeomPtrs& geo, const BinPtr
   // kernel, which writes the same words whenever it runs
   bwd_tile_order(c, bin, img, st);
   const uint32_t slots = (uint32_t)(c.gx * c.gy);
-#define GS_CWALK(EXACT)                                                                                        \
-  GS_LAUNCH("contrib_walk", k_contrib_walk<EXACT>, dim3(slots), dim3(64), 0, st, c, img.ranges, bin.point_list, \
-            bin.presort_gid, geo.splat, img.n_contrib, img.tile_max, img.tile_order, weights, rec)
-  if (exact_exp())
-    GS_CWALK(true);
-  else
-    GS_CWALK(false);
-#undef GS_CWALK
+  with_flag(exact_exp(), [&](auto EXACT) {
+    GS_LAUNCH("contrib_walk", k_contrib_walk<decltype(EXACT)::value>, dim3(slots), dim3(64), 0, st, c, img.ranges,
+              bin.point_list, bin.presort_gid, geo.splat, img.n_contrib, img.tile_max, img.tile_order, weights, rec);
+  });
   const dim3 grid((P + 64 * CSUM_WAVES - 1) / (64 * CSUM_WAVES)), block(64 * CSUM_WAVES);
   GS_LAUNCH("contrib_sum", k_contrib_sum, grid, block, 0, st, geo.counters, geo.offsets, geo.sorted_gid, geo.tiles,
             bin.slot_tile, img.tile_cut, img.cut_max, rec, (uint32_t)P, wsum, wmax, count, accumulate ? 1 : 0);

@@ -468,15 +468,11 @@ void feature_forward(int P, int C, const CameraArgs& c, const GeomPtrs& geo, con
   // same words whenever it runs
   bwd_tile_order(c, bin, img, st);
   const dim3 grid((uint32_t)(c.gx * c.gy), (uint32_t)((C + FEAT_G - 1) / FEAT_G));
-#define GS_FFWD(EXACT)                                                                                        \
-  GS_LAUNCH("feature_fwd", k_feature_fwd<EXACT>, grid, dim3(64), 0, st, c, img.ranges, bin.point_list,         \
-            bin.presort_gid, geo.splat, img.n_contrib, img.tile_max, img.tile_order, &geo.counters[CNT_ERR], \
-            features, C, out)
-  if (exact_exp())
-    GS_FFWD(true);
-  else
-    GS_FFWD(false);
-#undef GS_FFWD
+  with_flag(exact_exp(), [&](auto EXACT) {
+    GS_LAUNCH("feature_fwd", k_feature_fwd<decltype(EXACT)::value>, grid, dim3(64), 0, st, c, img.ranges,
+              bin.point_list, bin.presort_gid, geo.splat, img.n_contrib, img.tile_max, img.tile_order,
+              &geo.counters[CNT_ERR], features, C, out);
+  });
 }
 
 void feature_backward(int P, int C, const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, const ImgPtrs& img,
@@ -487,15 +483,11 @@ void feature_backward(int P, int C, const CameraArgs& c, const GeomPtrs& geo, co
   const dim3 sgrid((P + 64 * FSUM_WAVES - 1) / (64 * FSUM_WAVES)), sblock(64 * FSUM_WAVES);
   // the groups reuse the records in stream order
   for (int c0 = 0; c0 < C; c0 += FEAT_G) {
-#define GS_FWALK(EXACT)                                                                                         \
-  GS_LAUNCH("feature_bwd_walk", k_feature_bwd_walk<EXACT>, dim3(slots), dim3(64), 0, st, c, img.ranges,         \
-            bin.point_list, bin.presort_gid, geo.splat, img.n_contrib, img.tile_max, img.tile_order, dL_dout, C, \
-            c0, rec)
-    if (exact_exp())
-      GS_FWALK(true);
-    else
-      GS_FWALK(false);
-#undef GS_FWALK
+    with_flag(exact_exp(), [&](auto EXACT) {
+      GS_LAUNCH("feature_bwd_walk", k_feature_bwd_walk<decltype(EXACT)::value>, dim3(slots), dim3(64), 0, st, c,
+                img.ranges, bin.point_list, bin.presort_gid, geo.splat, img.n_contrib, img.tile_max, img.tile_order,
+                dL_dout, C, c0, rec);
+    });
     GS_LAUNCH("feature_sum", k_feature_sum, sgrid, sblock, 0, st, geo.counters, geo.offsets, geo.sorted_gid, geo.tiles,
               bin.slot_tile, img.tile_cut, img.cut_max, rec, (uint32_t)P, C, c0, dL_dfeatures, accumulate ? 1 : 0);
   }

@@ -392,55 +392,23 @@ void fwd_preprocess_grid(const GaussianArgs& g, const CameraArgs& c, int* radii,
                          dim3 grid, bool aa) {
   const dim3 block(256);
   if (aa) {  // whole SH rows or colours (the entry refuses split rows)
-#define GS_PRE_AA(D)                                                                                             \
-  GS_LAUNCH("preprocess", (k_preprocess_aa<D>), grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, \
-            geo.tiles, geo.clamped, geo.wg_tot)
-    switch (g.colors ? -1 : g.D) {
-      case -1: GS_PRE_AA(-1); break;
-      case 0: GS_PRE_AA(0); break;
-      case 1: GS_PRE_AA(1); break;
-      case 2: GS_PRE_AA(2); break;
-      default: GS_PRE_AA(3); break;
-    }
-#undef GS_PRE_AA
+    with_degree<-1>(g.colors ? -1 : g.D, [&](auto D) {
+      GS_LAUNCH("preprocess", (k_preprocess_aa<decltype(D)::value>), grid, block, 0, st, g, c, radii, geo.splat,
+                geo.binrec, geo.keys_a, geo.tiles, geo.clamped, geo.wg_tot);
+    });
     return;
   }
-  if (g.colors) {
-    GS_LAUNCH("preprocess", k_preprocess<-1>, grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, geo.tiles,
-              geo.clamped, geo.wg_tot);
+  if (g.shs_rest && !g.colors) {  // split SH rows (M >= 2, so D >= 0 applies)
+    with_degree(g.D, [&](auto D) {
+      GS_LAUNCH("preprocess", (k_preprocess_split<decltype(D)::value>), grid, block, 0, st, g, c, radii, geo.splat,
+                geo.binrec, geo.keys_a, geo.tiles, geo.clamped, geo.wg_tot);
+    });
     return;
   }
-  if (g.shs_rest) {  // split SH rows (M >= 2, so D >= 0 applies)
-#define GS_PRE_SPLIT(D)                                                                                        \
-  GS_LAUNCH("preprocess", (k_preprocess_split<D>), grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, \
-            geo.keys_a, geo.tiles, geo.clamped, geo.wg_tot)
-    switch (g.D) {
-      case 0: GS_PRE_SPLIT(0); break;
-      case 1: GS_PRE_SPLIT(1); break;
-      case 2: GS_PRE_SPLIT(2); break;
-      default: GS_PRE_SPLIT(3); break;
-    }
-#undef GS_PRE_SPLIT
-    return;
-  }
-  switch (g.D) {
-    case 0:
-      GS_LAUNCH("preprocess", k_preprocess<0>, grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, geo.tiles,
-                geo.clamped, geo.wg_tot);
-      break;
-    case 1:
-      GS_LAUNCH("preprocess", k_preprocess<1>, grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, geo.tiles,
-                geo.clamped, geo.wg_tot);
-      break;
-    case 2:
-      GS_LAUNCH("preprocess", k_preprocess<2>, grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, geo.tiles,
-                geo.clamped, geo.wg_tot);
-      break;
-    default:
-      GS_LAUNCH("preprocess", k_preprocess<3>, grid, block, 0, st, g, c, radii, geo.splat, geo.binrec, geo.keys_a, geo.tiles,
-                geo.clamped, geo.wg_tot);
-      break;
-  }
+  with_degree<-1>(g.colors ? -1 : g.D, [&](auto D) {
+    GS_LAUNCH("preprocess", (k_preprocess<decltype(D)::value>), grid, block, 0, st, g, c, radii, geo.splat, geo.binrec,
+              geo.keys_a, geo.tiles, geo.clamped, geo.wg_tot);
+  });
 }
 
 // K views in one launch.  Every lane forms the camera-independent half of its Gaussian once
@@ -483,29 +451,23 @@ __global__ __launch_bounds__(256) void k_preprocess_views(GaussianArgs g, PreVie
 void fwd_preprocess_views(const GaussianArgs& g0, const PreViews& pv, hipStream_t st) {
   launch_row_chunks(g0, st, [&](const GaussianArgs& g, dim3 grid) {
     const dim3 block(256);
-    if (g.colors) {
-      GS_LAUNCH("preprocess_views", (k_preprocess_views<-1, ROW_GLOBAL>), grid, block, 0, st, g, pv);
-      return;
-    }
-#define GS_PRE_VIEWS(D, SRC, lds) \
-  GS_LAUNCH("preprocess_views", (k_preprocess_views<D, SRC>), grid, block, lds, st, g, pv)
+    auto launch = [&](auto D, auto SRC, size_t lds) {
+      GS_LAUNCH("preprocess_views", (k_preprocess_views<decltype(D)::value, decltype(SRC)::value>), grid, block, lds, st,
+                g, pv);
+    };
+    using std::integral_constant;
+    if (g.colors) return launch(integral_constant<int, -1>{}, integral_constant<int, ROW_GLOBAL>{}, 0);
 #if GS_PREVIEWS_ROWS == 1
     if (sh_rows_stageable(g.D, g.M, g.shs)) {  // degrees 1 and 3
-      if (g.D == 1) GS_PRE_VIEWS(1, ROW_LDS, sh_stage_bytes(sh_row_floats(1)));
-      else GS_PRE_VIEWS(3, ROW_LDS, sh_stage_bytes(sh_row_floats(3)));
-      return;
+      constexpr integral_constant<int, ROW_LDS> LDS{};
+      if (g.D == 1) return launch(integral_constant<int, 1>{}, LDS, sh_stage_bytes(sh_row_floats(1)));
+      return launch(integral_constant<int, 3>{}, LDS, sh_stage_bytes(sh_row_floats(3)));
     }
     constexpr int SRC = ROW_GLOBAL;
 #else
     constexpr int SRC = ROW_REGS;
 #endif
-    switch (g.D) {
-      case 0: GS_PRE_VIEWS(0, SRC, 0); break;
-      case 1: GS_PRE_VIEWS(1, SRC, 0); break;
-      case 2: GS_PRE_VIEWS(2, SRC, 0); break;
-      default: GS_PRE_VIEWS(3, SRC, 0); break;
-    }
-#undef GS_PRE_VIEWS
+    with_degree(g.D, [&](auto D) { launch(D, integral_constant<int, SRC>{}, 0); });
   });
 }
 
@@ -1226,20 +1188,15 @@ void fwd_render(const CameraArgs& c, const GeomPtrs& geo, const BinPtrs& bin, co
                 hipStream_t st, uint32_t* err_host, const FwdAux& aux) {
   const int tiles = c.gx * c.gy;
   const int blocks = (int)xcd_span((uint32_t)tiles) * 32;
-#define GS_FWDQ(NAME, EXACT, AUX)                                                                           \
-  GS_LAUNCH(NAME, (k_render_fwd_q<EXACT, AUX>), dim3(blocks), dim3(64), 0, st, c, img.ranges, bin.point_list, \
-            bin.presort_gid, geo.splat, out_color, img, &geo.counters[CNT_ERR], err_host, aux)
-  if (aux.invdepth || aux.alpha) {  // the aux outputs: the AUX walk (gs_forward_render_aux)
-    if (exact_exp())
-      GS_FWDQ("render_fwd_aux", true, true);
-    else
-      GS_FWDQ("render_fwd_aux", false, true);
-  } else if (exact_exp()) {
-    GS_FWDQ("render_fwd", true, false);
-  } else {
-    GS_FWDQ("render_fwd", false, false);
-  }
-#undef GS_FWDQ
+  // the aux outputs: the AUX walk (gs_forward_render_aux)
+  with_flag(aux.invdepth || aux.alpha, [&](auto AUX) {
+    with_flag(exact_exp(), [&](auto EXACT) {
+      GS_LAUNCH(decltype(AUX)::value ? "render_fwd_aux" : "render_fwd",
+                (k_render_fwd_q<decltype(EXACT)::value, decltype(AUX)::value>), dim3(blocks), dim3(64), 0, st, c,
+                img.ranges, bin.point_list, bin.presort_gid, geo.splat, out_color, img, &geo.counters[CNT_ERR], err_host,
+                aux);
+    });
+  });
 }
 
 // ------------------------------------------------------------------------------------------

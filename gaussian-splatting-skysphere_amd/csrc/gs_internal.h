@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/gsrast.h"  // GS_ACC_* bits
 #include "gs_common.h"
@@ -443,6 +444,30 @@ __device__ __forceinline__ void timing_record(unsigned long long (*buf)[5], unsi
   }
 }
 #endif
+
+// ---- launch dispatch: a run-time SH degree or flag as a template argument ----
+// The stages below pick a kernel instantiation with these two and write its launch once, in a generic
+// lambda: with_flag(exact_exp(), [&](auto EXACT) { GS_LAUNCH(..., k<decltype(EXACT)::value>, ...); }).
+// with_degree<LO>(d, f): f(std::integral_constant<int, D>{}), D = d in LO..3; a degree above 3 goes to 3
+// and, with LO == -1 (the kernels' "no SH row": precomputed colours, no campos sums), a negative one to -1.
+template <int LO = 0, class F>
+inline void with_degree(int d, F&& f) {
+  static_assert(LO == 0 || LO == -1, "degrees 0..3, or -1..3");
+  if constexpr (LO < 0) {
+    if (d < 0) return f(std::integral_constant<int, -1>{});
+  }
+  switch (d) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+  }
+}
+template <class F>
+inline void with_flag(bool b, F&& f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
+}
 
 // ---- stages (gs_forward.hip / gs_backward.hip) ----
 // aa: the antialiased kernels (the opacity scaled by aa_scale; whole SH rows or colours only)
