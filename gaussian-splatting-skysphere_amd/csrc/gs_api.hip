@@ -283,6 +283,10 @@ bool exact_exp() {
 namespace gs {
 static std::atomic<uint32_t> g_spin_limit{LB_SPIN_LIMIT};
 uint32_t scan_spin_limit() { return g_spin_limit.load(std::memory_order_relaxed); }
+static std::atomic<int> g_tile_sort_packed{1};
+static std::atomic<long long> g_tile_sort_packed_n{0};
+bool tile_sort_packed() { return g_tile_sort_packed.load(std::memory_order_relaxed) != 0; }
+void tile_sort_packed_note() { g_tile_sort_packed_n.fetch_add(1, std::memory_order_relaxed); }
 
 // row waits installed by gs_set_row_waits, per host thread, until the next forward preprocess
 static thread_local RowWait t_row_waits[GS_MAX_ROW_WAITS];
@@ -1684,6 +1688,11 @@ int gs_knn_mean_dist2(int P, const float* points, float* out, void* scratch, voi
 unsigned gs_debug_set_scan_spin_limit(unsigned limit) {
   return gs::g_spin_limit.exchange(limit, std::memory_order_relaxed);
 }
+
+int gs_debug_set_tile_sort_packed(int on) {
+  return gs::g_tile_sort_packed.exchange(on ? 1 : 0, std::memory_order_relaxed);
+}
+long long gs_debug_tile_sort_packed_count(void) { return gs::g_tile_sort_packed_n.load(std::memory_order_relaxed); }
 
 int gs_debug_sh_rows_staged(int D, int M, const void* shs) { return gs::sh_rows_stageable(D, M, shs) ? 1 : 0; }
 

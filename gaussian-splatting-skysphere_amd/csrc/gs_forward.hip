@@ -12,7 +12,9 @@
 //   tile sort      stable radix sort of the instances by tile id only: because the input is
 //                  already depth-ordered (ties by Gaussian index) this equals upstream's sort by
 //                  the 64-bit key (tile << 32 | depth bits) with a ~3x smaller sort.
-//   k_ranges       per-tile [start, end) of the sorted list.
+//   k_ranges       per-tile [start, end) of the sorted list.  (Two-pass tile sorts of large enough
+//                  buffers run packed -- one word per instance, no sorted keys -- and take their
+//                  ranges from the second pass's histogram: tile_sort_packed_views.)
 //   k_render_fwd   one 256-lane workgroup (4 wave64) per 16x16 tile; Gaussians staged through LDS
 //                  256 at a time; front-to-back compositing with the block-wide early exit.
 #include "gs_internal.h"
@@ -903,6 +905,108 @@ __global__ __launch_bounds__(256) void k_ranges(uint32_t I, const uint32_t* __re
   }
 }
 
+// Tile ranges of the packed tile sort, without the sorted keys: one lane per tile t = (h, l), l its
+// low fb bits.  The second pass sorted the padded first-pass output, in which low digit l's region
+// covers the whole workgroups [tab[l], tab[l + 1]); its row-scanned histogram off2[h][b] counts the
+// words of high digit h in the workgroups before b, so tile t's instances are
+// base2[h] + [off2[h][tab[l]], off2[h][tab[l + 1]]) (a workgroup index at nb2: the row total).
+// Also clears the scheduling words, like k_ranges.
+__global__ __launch_bounds__(256) void k_ranges_packed(const uint32_t* __restrict__ off2,
+                                                       const uint32_t* __restrict__ row_total2, uint32_t nb2,
+                                                       const uint32_t* __restrict__ tab, int fb,
+                                                       uint2* __restrict__ ranges, uint32_t* __restrict__ sched,
+                                                       uint32_t n_sched, uint32_t tiles, uint64_t bs, uint64_t is) {
+  __shared__ uint32_t s_scan[4];
+  __shared__ uint32_t s_base2[RADIX], s_tot2[RADIX];
+  off2 = vptr(off2, bs), row_total2 = vptr(row_total2, bs), tab = vptr(tab, bs);
+  ranges = vptr(ranges, is), sched = vptr(sched, is);
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_sched; i += gridDim.x * 256) sched[i] = 0u;
+  const uint32_t rt = row_total2[threadIdx.x];
+  uint32_t all;
+  s_base2[threadIdx.x] = block_excl_scan(rt, s_scan, &all);
+  s_tot2[threadIdx.x] = rt;
+  lds_barrier();
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= tiles) return;
+  const uint32_t h = t >> fb, l = t & ((1u << fb) - 1u);
+  const uint32_t b0 = tab[l], b1 = tab[l + 1];
+  const uint32_t* row = off2 + (size_t)h * nb2;
+  const uint32_t x = b0 < nb2 ? row[b0] : s_tot2[h], y = b1 < nb2 ? row[b1] : s_tot2[h];
+  ranges[t] = x < y ? make_uint2(s_base2[h] + x, s_base2[h] + y) : make_uint2(0u, 0u);
+}
+
+// The packed two-pass tile sort: (tile, slot) as one word after the first pass, no key output from
+// the second, ranges from the second pass's histogram (k_ranges_packed).  It runs for two-pass
+// sorts (9 .. 16 tile bits) whose high digit and slot fit 32 bits, when the padded first-pass output
+// -- up to 2^fb chunks more than the I instances -- fits the 2 I words of keys_b | vals_b, both
+// unused by this path.  Everything else takes radix_sort_pairs + k_ranges.
+struct PackedPlan {
+  int fb, hb;
+  uint32_t sb;      // bits of the slot field: I < 2^sb
+  SortPlan p1;      // first pass, over the I slots
+  uint32_t n2_max;  // words of the padded intermediate
+  uint32_t nb2;     // second-pass workgroups (of p1.chunk words)
+};
+static bool packed_plan(uint32_t I, int tbits, PackedPlan* pp) {
+  if (radix_passes(tbits) != 2) return false;
+  pp->fb = radix_first_bits(tbits), pp->hb = tbits - pp->fb;
+  pp->sb = 1;
+  while (pp->sb < 32 && ((uint64_t)1 << pp->sb) <= (uint64_t)I) pp->sb++;
+  if ((uint32_t)pp->hb + pp->sb > 32) return false;
+  pp->p1 = sort_plan(I, GS_TILE_SORT_BLOCKS);
+  const uint64_t pad = (uint64_t)pp->p1.chunk << pp->fb;
+  // (32-bit positions: a position plus one chunk stays below 2^32)
+  if (pad > (uint64_t)I || (uint64_t)I + pad + pp->p1.chunk >= ((uint64_t)1 << 32)) return false;
+  pp->n2_max = (uint32_t)(I + pad);
+  pp->nb2 = (pp->n2_max + pp->p1.chunk - 1) / pp->p1.chunk;  // = p1.nb + 2^fb <= the scratch's columns
+  return true;
+}
+
+static void tile_sort_packed_views(int views, uint32_t I, const PackedPlan& pp, bool hist0, const BinPtrs& bin,
+                                   const ImgPtrs& img, uint32_t tiles, uint32_t sched_n, uint64_t bs, uint64_t is,
+                                   hipStream_t st) {
+  const SortPlan& p = pp.p1;
+  uint32_t* hist = bin.sort_scratch;
+  uint32_t* padded = bin.keys_b;  // keys_b | vals_b
+  const PackArgs pk{pp.sb, bin.pack_tab};
+  if (!hist0)
+    GS_LAUNCH("radix_hist", k_radix_hist<NoFin>, dim3(p.nb, views), dim3(SORT_THREADS), 0, st, bin.slot_tile,
+              bin.count, I, 0, pp.fb, p.chunk, p.nb, hist, false, bs, NoFin());
+  uint32_t* row_total = hist + (size_t)RADIX * p.nb;
+  GS_LAUNCH("radix_rowscan", k_radix_rowscan<>, dim3(RADIX, views), dim3(SORT_THREADS), 0, st, hist, p.nb, row_total,
+            bs);
+  auto with_bits = [](int bits, auto&& f) {
+    switch (bits) {
+      case 8: return f(std::integral_constant<int, 8>{});
+      case 7: return f(std::integral_constant<int, 7>{});
+      case 6: return f(std::integral_constant<int, 6>{});
+      case 5: return f(std::integral_constant<int, 5>{});
+      default: return f(std::integral_constant<int, 4>{});
+    }
+  };
+  with_bits(pp.fb, [&](auto B) {
+    GS_LAUNCH("radix_scatter", (k_radix_scatter<false, decltype(B)::value, 3>), dim3(p.nb, views), dim3(SORT_THREADS),
+              0, st, bin.slot_tile, nullptr, padded, nullptr, bin.count, I, 0, p.chunk, p.nb, hist, row_total, false,
+              nullptr, nullptr, bs, pk);
+  });
+  // second pass: the padded words, bounded by the padded total (device)
+  const uint32_t* n2 = bin.pack_tab + PACK_TAB_TOTAL;
+  GS_LAUNCH("radix_hist", k_radix_hist<NoFin>, dim3(pp.nb2, views), dim3(SORT_THREADS), 0, st, padded, n2, pp.n2_max,
+            (int)pp.sb, pp.hb, p.chunk, pp.nb2, hist, true, bs, NoFin());
+  row_total = hist + (size_t)RADIX * pp.nb2;
+  GS_LAUNCH("radix_rowscan", k_radix_rowscan<>, dim3(RADIX, views), dim3(SORT_THREADS), 0, st, hist, pp.nb2, row_total,
+            bs);
+  with_bits(pp.hb, [&](auto B) {
+    if constexpr (decltype(B)::value >= 5)  // (hb >= 5: two-pass sorts start at 4 + 5 bits)
+      GS_LAUNCH("radix_scatter", (k_radix_scatter<false, decltype(B)::value, 4>), dim3(pp.nb2, views),
+                dim3(SORT_THREADS), 0, st, padded, nullptr, nullptr, bin.point_list, n2, pp.n2_max, (int)pp.sb, p.chunk,
+                pp.nb2, hist, row_total, true, nullptr, nullptr, bs, pk);
+  });
+  GS_LAUNCH("ranges", k_ranges_packed, dim3((tiles + 255) / 256, views), dim3(256), 0, st, hist, row_total, pp.nb2,
+            bin.pack_tab, pp.fb, img.ranges, (uint32_t*)img.tile_done, sched_n, tiles, bs, is);
+  tile_sort_packed_note();
+}
+
 void fwd_bin(int P, uint32_t I, const CameraArgs& c, const int* radii, const GeomPtrs& geo, const BinPtrs& bin,
              const ImgPtrs& img, hipStream_t st) {
   (void)radii;
@@ -946,6 +1050,11 @@ void fwd_bin_views(int views, int P, uint32_t I, const CameraArgs& c, const Geom
             geo.counters, geo.dup_first, geo.sorted_gid, geo.offsets, geo.binrec, c.gx, c.gy, bin.slot_tile,
             bin.presort_gid, img.ranges, hist0 ? bin.sort_scratch : nullptr, (1u << radix_first_bits(tbits)) - 1u,
             bin.count, gs, bs, is);
+  PackedPlan pp;
+  if (tile_sort_packed() && packed_plan(I, tbits, &pp)) {
+    tile_sort_packed_views(views, I, pp, hist0, bin, img, (uint32_t)tiles, sched_n, bs, is, st);
+    return;
+  }
   // the device count bounds the sort (I is the buffers' capacity, which may exceed it)
   radix_sort_pairs(bin.keys_a, bin.vals_a, bin.keys_b, bin.vals_b, true, bin.count, I, tbits, bin.sort_scratch, st,
                    false, hist0, nullptr, nullptr, nullptr, bin.slot_tile,

@@ -7,7 +7,8 @@
 //                                    clamped u8 | depth-sort keys/vals x2 u32 (keys_a: depth keys
 //                                    written by preprocess) | offsets u32 |
 //                                    scan partials | sort scratch | counters
-//   binning   (per instance, I)      tile keys/vals x2 u32 | presort_gid u32 | sort scratch
+//   binning   (per instance, I)      tile keys/vals x2 u32 | presort_gid u32 | sort scratch |
+//                                    count | packed tile sort's region table
 //   image     (per pixel / tile)     ranges uint2 | final_T f32 | n_contrib u32 | tile_max u32 x4
 //                                    (largest n_contrib of each 8x8 quadrant) | tile_order u32 |
 //                                    tile_cut u32 | tile_done u64 + length buckets | bucket rank u32
@@ -289,12 +290,22 @@ struct BinPtrs {
   uint32_t* presort_gid;
   uint32_t* sort_scratch;
   uint32_t* point_list;  // sorted presort slots (= vals_a or vals_b after the tile sort)
-  uint32_t* sorted_tile;
+  uint32_t* sorted_tile;  // the sorted keys, for k_ranges (not written by the packed tile sort)
   uint32_t* slot_tile;   // tile of every instance slot (duplicate output, kept: the tile sort's
                          // first pass reads it and writes keys_b)
   uint32_t* count;       // [0]: the view's instance count bounded by the buffer's capacity (the duplicate
                          // writes it; the tile sort and k_ranges read it from this buffer)
+  uint32_t* pack_tab;    // the packed tile sort's region table and padded total (PACK_TAB_WORDS)
 };
+
+// The packed two-pass tile sort (fwd_bin_views): its second pass counts and scatters
+// the padded first-pass output, which has up to RADIX more workgroups than the plain sort of the
+// same count: RADIX more columns of the [digit][block] histogram.
+constexpr size_t PACK_SCRATCH_WORDS = (size_t)RADIX * RADIX;
+// process-wide switch (gs_debug_set_tile_sort_packed; default on) and the count of binnings that
+// took the packed path (gs_debug_tile_sort_packed_count), gs_api.hip
+bool tile_sort_packed();
+void tile_sort_packed_note();
 
 
 // (Tried in round 2 and not kept: the forward's quadrant waves storing each staged entry's 48-B splat
@@ -318,10 +329,13 @@ inline size_t bin_layout(size_t I, int tiles, BinPtrs* out, char* base) {
   size_t In = I ? I : 1;
   size_t o_ka = take(In * 4), o_va = take(In * 4), o_kb = take(In * 4), o_vb = take(In * 4);
   size_t o_pg = take(In * 4), o_st = take(In * 4);
-  size_t o_ss = take(sort_scratch_words(In) * 4);
+  // (both additions for the packed tile sort are constants: the size stays monotone in the count)
+  size_t o_ss = take((sort_scratch_words(In) + PACK_SCRATCH_WORDS) * 4);
   size_t o_cn = take(64);
+  size_t o_pt = take(PACK_TAB_WORDS * 4);
   if (out && base) {
     out->count = (uint32_t*)(base + o_cn);
+    out->pack_tab = (uint32_t*)(base + o_pt);
     out->keys_a = (uint32_t*)(base + o_ka);
     out->vals_a = (uint32_t*)(base + o_va);
     out->keys_b = (uint32_t*)(base + o_kb);

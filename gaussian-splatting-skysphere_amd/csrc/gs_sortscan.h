@@ -504,26 +504,63 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_rowscan(uint32_t* __rest
 // aux_in[value], the table in the order of the sorted keys (a value >= n_max reads as 0).
 // EXTRA 2 (a first pass with identity values, at most 2^PACK_ID_BITS keys): the value of key i is
 // i | min(aux_in[i], PACK_MAX) << PACK_ID_BITS.
+// EXTRA 3 / 4: the two passes of the packed tile sort (gs_forward.hip tile_sort_packed_views), one
+// word per key and one stream through LDS.
+// EXTRA 3 (first pass, identity values): key i leaves as (key >> BITS) << pk.sb | i, into keys_out
+// only, in a padded layout: digit d's region starts at the sum of the earlier digits' totals, each
+// rounded up to `chunk`, so every region starts at a workgroup boundary of the next pass.  The gaps
+// are filled with DEPTH_DROP; workgroup 0 writes the regions' first workgroups and the padded total
+// into pk.tab (PACK_TAB_*).
+// EXTRA 4 (second pass, drop on): sorts the words by their digit at `shift` (= pk.sb) and writes
+// only word & (2^pk.sb - 1) to vals_out.
+struct PackArgs {
+  uint32_t sb = 0;          // bits of the slot field
+  uint32_t* tab = nullptr;  // PACK_TAB_WORDS words in the view's binning buffer
+};
+// pk.tab: [l] first pass-2 workgroup of low digit l's region, l = 0 .. RADIX (RADIX: the end);
+// [PACK_TAB_TOTAL] the padded total, pass 2's device count
+constexpr int PACK_TAB_TOTAL = (1 << 8) + 1, PACK_TAB_WORDS = (1 << 8) + 16;
+constexpr int PACK_LOCAL_BITS = 11;  // a key's index inside its 2048-key tile
 template <bool AUX, int BITS, int EXTRA = 0>
 __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
     const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t* __restrict__ keys_out,
     uint32_t* __restrict__ vals_out, const uint32_t* n_dev, uint32_t n_max, int shift, uint32_t chunk,
     uint32_t nb, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ row_total, bool drop,
-    const uint32_t* __restrict__ aux_in, uint32_t* __restrict__ aux_out, uint64_t vstride) {
+    const uint32_t* __restrict__ aux_in, uint32_t* __restrict__ aux_out, uint64_t vstride,
+    PackArgs pk = PackArgs()) {
+  constexpr bool PACKED = EXTRA == 3 || EXTRA == 4;
+  static_assert(!(PACKED && AUX), "the packed tile sort carries no second stream");
   __shared__ uint32_t s_base[RADIX];      // global position of the next key of each digit
   __shared__ uint32_t s_wcnt[4][RADIX];   // per-wave running counts -> per-wave exclusive prefix
   __shared__ uint32_t s_loc[RADIX];       // digit offsets inside the tile (for the LDS reorder)
   __shared__ uint32_t s_tot[RADIX];
   __shared__ uint32_t s_scan[4];
   __shared__ uint32_t s_key[SORT_TILE];
-  __shared__ uint32_t s_val[SORT_TILE];
+  __shared__ uint32_t s_val[PACKED ? 1 : SORT_TILE];
   __shared__ uint32_t s_aux[AUX ? SORT_TILE : 1];
   keys_in = vptr(keys_in, vstride), vals_in = vptr(vals_in, vstride), keys_out = vptr(keys_out, vstride);
   vals_out = vptr(vals_out, vstride), n_dev = vptr(n_dev, vstride), hist = vptr(hist, vstride);
   row_total = vptr(row_total, vstride), aux_in = vptr(aux_in, vstride), aux_out = vptr(aux_out, vstride);
   const uint32_t n = resolve_n(n_dev, n_max);
   const uint32_t tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
-  {
+  if constexpr (EXTRA == 3) {
+    uint32_t* tab = vptr(pk.tab, vstride);
+    const uint32_t rt = row_total[tid], rt_pad = (rt + chunk - 1) / chunk * chunk;
+    uint32_t all;
+    const uint32_t digit_base = block_excl_scan(rt_pad, s_scan, &all);
+    s_base[tid] = digit_base + hist[(size_t)tid * nb + blockIdx.x];
+    if (blockIdx.x == 0) {
+      tab[tid] = digit_base / chunk;
+      if (tid == 0) tab[RADIX] = all / chunk, tab[PACK_TAB_TOTAL] = all;
+    }
+    // the gap behind digit d's keys: workgroup d % nb fills it
+    s_loc[tid] = digit_base + rt;
+    s_tot[tid] = rt_pad - rt;
+    lds_barrier();
+    for (uint32_t d = blockIdx.x; d < (1u << BITS); d += nb)
+      for (uint32_t k = tid; k < s_tot[d]; k += SORT_THREADS) keys_out[s_loc[d] + k] = DEPTH_DROP;
+    lds_barrier();
+  } else {
     uint32_t all;
     const uint32_t digit_base = block_excl_scan(row_total[tid], s_scan, &all);
     s_base[tid] = digit_base + hist[(size_t)tid * nb + blockIdx.x];
@@ -546,6 +583,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
       const bool v = i < end;
       key[r] = v ? keys_in[i] : 0xFFFFFFFFu;
       if constexpr (EXTRA == 2) val[r] = v ? (i | (min(aux_in[i], PACK_MAX) << PACK_ID_BITS)) : 0u;
+      else if constexpr (PACKED) val[r] = 0u;
       else val[r] = v ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
       if constexpr (AUX) aux[r] = v ? aux_in[i] : 0u;
     }
@@ -583,8 +621,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
       if (i < end && !(drop && key[r] == DEPTH_DROP)) {
         const uint32_t d = (key[r] >> shift) & mask;
         const uint32_t slot = s_loc[d] + s_wcnt[wid][d] + rank[r];
-        s_key[slot] = key[r];
-        s_val[slot] = val[r];
+        // (EXTRA 3: the key beside its index in the tile -- at most 16 + 11 bits)
+        if constexpr (EXTRA == 3) s_key[slot] = key[r] << PACK_LOCAL_BITS | (i - t0);
+        else s_key[slot] = key[r];
+        if constexpr (!PACKED) s_val[slot] = val[r];
         if constexpr (AUX) s_aux[slot] = aux[r];
       }
     }
@@ -596,10 +636,16 @@ __global__ __launch_bounds__(SORT_THREADS) void k_radix_scatter(
       const uint32_t slot = (uint32_t)r * SORT_THREADS + tid;
       if (slot < ntile) {
         const uint32_t k = s_key[slot];
-        const uint32_t d = (k >> shift) & mask;
+        const uint32_t d = (k >> (EXTRA == 3 ? PACK_LOCAL_BITS : shift)) & mask;
         const uint32_t pos = s_base[d] + (slot - s_loc[d]);
-        keys_out[pos] = k;
-        vals_out[pos] = s_val[slot];
+        if constexpr (EXTRA == 3) {
+          keys_out[pos] = (k >> (PACK_LOCAL_BITS + BITS)) << pk.sb | (t0 + (k & ((1u << PACK_LOCAL_BITS) - 1u)));
+        } else if constexpr (EXTRA == 4) {
+          vals_out[pos] = k & ((1u << pk.sb) - 1u);
+        } else {
+          keys_out[pos] = k;
+          vals_out[pos] = s_val[slot];
+        }
         if constexpr (AUX) aux_out[pos] = s_aux[slot];
         if constexpr (EXTRA == 1) {
           const uint32_t g = s_val[slot];

@@ -255,6 +255,8 @@ SIGNATURES = {
     ),
     "gs_debug_export_slots": (_c_i, [_c_i, _c_i, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gs_debug_set_scan_spin_limit": (ctypes.c_uint, [ctypes.c_uint]),
+    "gs_debug_set_tile_sort_packed": (_c_i, [_c_i]),
+    "gs_debug_tile_sort_packed_count": (_c_ll, []),
     "gs_debug_sh_rows_staged": (_c_i, [_c_i, _c_i, _c_p]),
     "gs_profile_enable": (None, [_c_i]),
     "gs_profile_collect": (_c_i, []),

@@ -943,6 +943,13 @@ int gs_debug_export(int P, int image_width, int image_height, long long num_rend
  * "look-back wait timed out" (gs_forward_render).  Returns the previous limit (default 1 << 22). */
 unsigned gs_debug_set_scan_spin_limit(unsigned limit);
 
+/* ---- test hook: the packed two-pass tile sort (process-wide, default on) ----
+ * 0 sends every binning through the (key, slot) pair sort and the key-reading range kernel; the
+ * lists, ranges and everything after them are the same either way.  Returns the previous value.
+ * gs_debug_tile_sort_packed_count: binnings that took the packed path since load. */
+int gs_debug_set_tile_sort_packed(int on);
+long long gs_debug_tile_sort_packed_count(void);
+
 /* ---- test hook: eligibility of an SH layout for the K-view preprocess's LDS-staged row loader ----
  * 1 for rows of exactly M = (D + 1)^2 coefficients that are whole 16-B pieces (3 M a multiple of
  * 4) at a 16-B aligned `shs`, else 0.  A library built with -DGS_PREVIEWS_ROWS=1 launches
