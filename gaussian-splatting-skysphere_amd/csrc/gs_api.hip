@@ -1635,6 +1635,12 @@ int gs_backward_gaussians_adam_stats_aux(int P, int D, int M, const float* means
   if (means3D != params_host[DT_XYZ]) return set_error("means3D must be the xyz parameter (params_host[0])"), 1;
   if (((uintptr_t)params_host[DT_ROT]) & 15) return set_error("rotation parameter must be 16-byte aligned"), 1;
   if ((((uintptr_t)shs_dc) | ((uintptr_t)shs_rest)) & 15) return set_error("split SH rows must be 16-byte aligned"), 1;
+  // the kernel's 16-B accesses (adam_sh_block, the rotation rows): the parameter and both moments of these groups
+  static const struct { int k; const char* name; } vec_groups[] = {
+      {DT_FDC, "features_dc"}, {DT_FREST, "features_rest"}, {DT_ROT, "rotation"}};
+  for (const auto& vg : vec_groups)
+    if ((((uintptr_t)params_host[vg.k]) | ((uintptr_t)exp_avg_host[vg.k]) | ((uintptr_t)exp_avg_sq_host[vg.k])) & 15)
+      return set_error("fused Adam backward: %s parameter, exp_avg and exp_avg_sq must be 16-byte aligned", vg.name), 1;
   const GaussianArgs g = make_scene(P, D, M, means3D, shs_dc, shs_rest, nullptr, nullptr, scales, scale_modifier,
                                     rotations, nullptr);
   FusedAdamArgs a{};

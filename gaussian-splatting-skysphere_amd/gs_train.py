@@ -265,6 +265,11 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("step_fused_backward: the six groups must share betas, eps and maximize")
         if rot.data_ptr() % 16:
             raise ValueError("step_fused_backward: the rotation parameter must be 16-byte aligned")
+        # the kernel's 16-byte accesses: the parameter and both moments of these three groups
+        for name, k in (("features_dc", 1), ("features_rest", 2), ("rotation", 5)):
+            if any(t.data_ptr() % 16 for t in (params[k], ms[k], vs[k])):
+                raise ValueError(f"step_fused_backward: {name} parameter, exp_avg and exp_avg_sq must be 16-byte "
+                                 "aligned")
         mean3, sh, sh_rest = inputs["means3D"], inputs["sh"], inputs.get("sh_rest")
         if mean3.data_ptr() != xyz.data_ptr() or sh_rest is None or sh.data_ptr() != dc.data_ptr() or \
                 sh_rest.data_ptr() != rest.data_ptr():

@@ -826,7 +826,10 @@ int gs_adam_step_activated(int count, float* const* params_host, const float* co
  * params / exp_avg / exp_avg_sq: HOST arrays of 6 DEVICE pointers in group order xyz [P,3],
  * f_dc [P,1,3], f_rest [P,15,3], opacity [P,1], scaling [P,3], rotation [P,4] (raw parameters,
  * rotation 16-byte aligned); lr / step / weight_decay per group as gs_adam_step (weight_decay_host
- * may be NULL).  The Adam update runs in place while the kernel reads the parameters: nothing else
+ * may be NULL).  The kernel reads and writes f_dc, f_rest and rotation with 16-byte accesses: the
+ * parameter, exp_avg and exp_avg_sq pointers of these three groups must all be 16-byte aligned, and
+ * the call is refused before any launch otherwise (one message, naming the group); the other three
+ * groups' tensors need only float alignment.  The Adam update runs in place while the kernel reads the parameters: nothing else
  * may read or write them on another stream until the call's work completes.  A view whose forward
  * recorded an error (its geometry buffer's flags: capacity overflow, look-back timeout, culled
  * prefiltered point) is not updated, so a caller may launch this before reading the forward's status

@@ -307,12 +307,17 @@ def gaussians_rows(e):
     ]
 
 
-def adam_rows(e):
-    def six(k, v):
-        a = [X] * 6
-        a[k] = v
-        return ptrs(*a)
+E_ADAM_ALIGN = "fused Adam backward: %s parameter, exp_avg and exp_avg_sq must be 16-byte aligned"
 
+
+def six(k, v):
+    """Six valid-looking group pointers (xyz, f_dc, f_rest, opacity, scaling, rotation) with group k's set to v."""
+    a = [X] * 6
+    a[k] = v
+    return ptrs(*a)
+
+
+def adam_rows(e):
     return [
         (e, dict(P=-1, M=15), 1, E_P, None),
         (e, dict(P=0, M=15, means3D=None), 0, "", None),
@@ -499,6 +504,21 @@ def build_rows():
             (e, dict(shs=None, colors=X, D=9, M=0, dsh=None, dcolors=None, dcov3D=None, dscales=None, drots=None,
                      view_list=views(view(image_width=0))), 1, "view 0: bad image size", None),
         ]
+    # ---- the fused Adam kernel's 16-byte accesses: the parameter and both moments of features_dc, features_rest
+    # ---- and rotation, checked behind the SH rows' alignment (gs_backward_gaussians_adam forwards to
+    # ---- gs_backward_gaussians_adam_stats_aux, whose own rows are in tests/test_sky_train_cpu.py).  Appended here.
+    e = "gs_backward_gaussians_adam"
+    for k, name in ((1, "features_dc"), (2, "features_rest"), (5, "rotation")):
+        for arg in ("params", "exp_avg", "exp_avg_sq"):
+            if (k, arg) != (5, "params"):  # (its own, older message: adam_rows)
+                rows.append((e, {arg: six(k, ODD)}, 1, E_ADAM_ALIGN % name, None))
+    rows += [
+        (e, dict(exp_avg=six(2, ODD), shs_rest=ODD), 1, "split SH rows must be 16-byte aligned", None),
+        (e, dict(exp_avg_sq=six(1, ODD), means3D=OTHER), 1, "means3D must be the xyz parameter (params_host[0])", None),
+        # (several: the first in group order is named)
+        (e, dict(exp_avg=ptrs(X, ODD, ODD, X, X, ODD)), 1, E_ADAM_ALIGN % "features_dc", None),
+        (e, dict(exp_avg=six(5, ODD), P=0), 0, "", None),
+    ]
     return rows
 
 

@@ -110,7 +110,27 @@ def _size_limit_rows():
     return rows
 
 
-ROWS = _render_rows() + _adam_rows() + _size_limit_rows()
+def _alignment_rows():
+    """The fused kernel's 16-byte accesses (tests/test_api_contract_cpu.py, behind every earlier row): the
+    parameter and both moments of features_dc, features_rest and rotation, with and without the aux sums,
+    in front of the statistics' checks; the scalar groups' moments may sit anywhere."""
+    a = "gs_backward_gaussians_adam_stats_aux"
+    rows = []
+    for k, name in ((1, "features_dc"), (2, "features_rest"), (5, "rotation")):
+        for arg in ("params", "exp_avg", "exp_avg_sq"):
+            if (k, arg) != (5, "params"):
+                rows.append((a, {arg: tc.six(k, ODD)}, 1, tc.E_ADAM_ALIGN % name))
+    rows += [
+        (a, dict(exp_avg=tc.six(2, ODD), invdepth_sums=None), 1, tc.E_ADAM_ALIGN % "features_rest"),
+        (a, dict(exp_avg_sq=tc.six(5, ODD), st_radii=X), 1, tc.E_ADAM_ALIGN % "rotation"),
+        (a, dict(exp_avg=tc.six(1, ODD), shs=ODD), 1, "split SH rows must be 16-byte aligned"),
+        (a, dict(exp_avg=tc.ptrs(ODD, X, X, ODD, ODD, X), exp_avg_sq=tc.ptrs(ODD, X, X, ODD, ODD, X), st_radii=X), 1,
+         "densify stats: all five pointers or none"),
+    ]
+    return rows
+
+
+ROWS = _render_rows() + _adam_rows() + _size_limit_rows() + _alignment_rows()
 
 
 def _id(i, row):

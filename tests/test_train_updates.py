@@ -70,6 +70,81 @@ def test_adam_abi_validation_without_gpu():
     assert lib.gs_backward_gaussians_adam_stats(0, *base[1:], *some, 0, None) == 0  # P == 0: nothing to do
 
 
+def test_fused_backward_adam_alignment_contract_without_gpu(monkeypatch):
+    """The fused backward + Adam kernel reads and writes features_dc, features_rest and rotation with 16-byte
+    accesses: gs_backward_gaussians_adam_stats_aux refuses, before any launch, a parameter, exp_avg or
+    exp_avg_sq pointer of these groups that is not 16-byte aligned (fake host pointers: an accepted call
+    would fault here), and FusedAdam.prepare_fused_backward raises ValueError for the same tensors."""
+    import ctypes
+
+    import gs_train
+    from diff_gaussian_rasterization import _native
+
+    lib = _native.load()
+    good = [0x10000 * (k + 1) for k in range(6)]
+    steps = ctypes.cast((ctypes.c_longlong * 6)(*[1] * 6), ctypes.c_void_p)
+    lrs = ctypes.cast((ctypes.c_double * 6)(*[1e-3] * 6), ctypes.c_void_p)
+    vg = _native.ViewGrad(0x1000, 0x2000, 0x3000, 0.5, 0.5, 8, 8, 0x4000)
+
+    def call(which, k, off, sums):
+        arrs = [list(good), list(good), list(good)]
+        arrs[which][k] += off
+        p, m, v = (ctypes.cast((ctypes.c_void_p * 6)(*a), ctypes.c_void_p) for a in arrs)
+        # (statistics: one pointer of five, so a call that passes the alignment check stops at the next one)
+        rc = lib.gs_backward_gaussians_adam_stats_aux(
+            5, 3, 16, ctypes.c_void_p(good[0]), ctypes.c_void_p(good[1]), ctypes.c_void_p(good[2]),
+            ctypes.c_void_p(0x9000), 1.0, ctypes.c_void_p(0xA000), ctypes.byref(vg), p, m, v, lrs, steps, None, 0.9,
+            0.999, 1e-15, 0, ctypes.c_void_p(0xB000), None, 2, None, None, None, sums, 0, None)
+        return rc, _native.last_error()
+
+    names = {1: "features_dc", 2: "features_rest", 5: "rotation"}
+    for sums in (None, ctypes.c_void_p(0xC000)):
+        for which in (1, 2):  # exp_avg, exp_avg_sq
+            for k in range(6):
+                for off in (4, 8, 12):
+                    rc, err = call(which, k, off, sums)
+                    assert rc != 0
+                    if k in names:
+                        assert err == (f"fused Adam backward: {names[k]} parameter, exp_avg and exp_avg_sq must be "
+                                       "16-byte aligned"), (which, k, err)
+                    else:  # xyz, opacity, scaling: scalar accesses
+                        assert "all five pointers or none" in err, (which, k, err)
+        rc, err = call(0, 2, 4, sums)  # (params[1] is shs_dc and params[5] has its older message: api contract table)
+        assert rc != 0 and "features_rest parameter, exp_avg and exp_avg_sq" in err
+        assert "all five pointers or none" in call(0, 0, 0, sums)[1]
+
+    # prepare_fused_backward: host tensors stand in for device ones (the device check is patched out);
+    # a view at a 4-byte offset of its storage is not 16-byte aligned
+    monkeypatch.setattr(gs_train, "_check_f32_dense", lambda t, what: None)
+    P = 5
+    shapes = ((P, 3), (P, 1, 3), (P, 15, 3), (P, 1), (P, 3), (P, 4))
+
+    def tensor(shape, off):
+        n = 1
+        for s in shape:
+            n *= s
+        base = torch.zeros(n + 8)
+        lead = (-base.data_ptr() % 16) // 4  # floats up to the next 16-byte boundary
+        return base[lead + off:lead + off + n].view(shape)
+
+    for which in ("param", "exp_avg", "exp_avg_sq", None):
+        for k in (1, 2, 5):
+            ps = [torch.nn.Parameter(tensor(s, 1 if (which == "param" and j == k) else 0))
+                  for j, s in enumerate(shapes)]
+            opt = gs_train.FusedAdam([{"params": [p], "lr": 1e-3} for p in ps], lr=0.0, eps=1e-15)
+            for j, (p, s) in enumerate(zip(ps, shapes)):
+                off = lambda w, o: o if (which == w and j == k) else 0  # noqa: E731
+                opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": tensor(s, off("exp_avg", 1)),
+                                "exp_avg_sq": tensor(s, off("exp_avg_sq", 3))}
+            if which is None:  # aligned: the next check answers (no deferred view was given)
+                with pytest.raises(ValueError, match="the deferred view must have read"):
+                    opt.prepare_fused_backward(ps, {"means3D": ps[1], "sh": ps[1], "sh_rest": None}, None)
+            else:
+                with pytest.raises(ValueError, match="16-byte aligned") as e:
+                    opt.prepare_fused_backward(ps, {}, None)
+                assert names[k] in str(e.value) or (k == 5 and which == "param"), str(e.value)
+
+
 def _make_params(device, sizes, seed=0):
     g = torch.Generator().manual_seed(seed)
     return [torch.randn(s, generator=g).to(device) for s in sizes]
