@@ -46,8 +46,7 @@ struct Fns {
   decltype(&gs_forward_bin_views) bin_views = nullptr;
   decltype(&gs_forward_render_binned) render_binned = nullptr;
   decltype(&gs_backward_render) bwd_render = nullptr;
-  decltype(&gs_backward_accumulate) backward = nullptr;
-  decltype(&gs_backward_accumulate_split) backward_split = nullptr;
+  decltype(&gs_backward_accumulate_absgrad) backward = nullptr;
   decltype(&gs_backward_gaussians_range) bwd_gaussians = nullptr;
   decltype(&gs_geom_buffer_bytes) geom_bytes = nullptr;
   decltype(&gs_binning_buffer_bytes) binning_bytes = nullptr;
@@ -80,8 +79,7 @@ void init() {
   resolve(F.bin_views, "gs_forward_bin_views");
   resolve(F.render_binned, "gs_forward_render_binned");
   resolve(F.bwd_render, "gs_backward_render");
-  resolve(F.backward, "gs_backward_accumulate");
-  resolve(F.backward_split, "gs_backward_accumulate_split");
+  resolve(F.backward, "gs_backward_accumulate_absgrad");
   resolve(F.bwd_gaussians, "gs_backward_gaussians_range");
   resolve(F.geom_bytes, "gs_geom_buffer_bytes");
   resolve(F.binning_bytes, "gs_binning_buffer_bytes");
@@ -364,24 +362,15 @@ py::tuple backward(const at::Tensor& background, const at::Tensor& means3D, cons
   R = layout_count((long long)R, binning, W, H);
   at::Tensor scratch = at::empty({(int64_t)F.grad_bytes((long long)R)}, f32o.dtype(at::kByte));
   const at::Tensor sc_out = has_sr ? g_sc : at::Tensor(), rot_out = has_sr ? g_rot : at::Tensor();
-  if (x.sh_rest.defined()) {  // split SH rows: SH colours, so no dL/dcolors output
-    check(F.backward_split((int)P, (int)degree, (int)M, fp(x.bg), (int)W, (int)H, fp(x.means3D), fp(x.sh),
-                           fp(x.sh_rest), fp(x.opacity), fp(x.scales), (float)scale_modifier, fp(x.rotations),
-                           fp(x.cov3D), fp(x.view), fp(x.proj), fp(x.campos), (float)tan_fovx, (float)tan_fovy,
-                           radii.data_ptr<int>(), geom.data_ptr(), (long long)R, binning.data_ptr(), img.data_ptr(),
-                           fp(dpix), scratch.data_ptr(), g_m2.data_ptr<float>(), g_op.data_ptr<float>(),
-                           g_m3.data_ptr<float>(), (float*)vp(g_cov), (float*)vp(g_sh), (float*)vp(sc_out),
-                           (float*)vp(rot_out), acc, reinterpret_cast<void*>(wait_event), (int)debug, st),
-          "rasterize_gaussians_backward");
-    return result();
-  }
-  check(F.backward((int)P, (int)degree, (int)M, fp(x.bg), (int)W, (int)H, fp(x.means3D), fp(x.sh), fp(x.colors),
-                   fp(x.opacity), fp(x.scales), (float)scale_modifier, fp(x.rotations), fp(x.cov3D), fp(x.view),
-                   fp(x.proj), fp(x.campos), (float)tan_fovx, (float)tan_fovy, radii.data_ptr<int>(), geom.data_ptr(),
-                   (long long)R, binning.data_ptr(), img.data_ptr(), fp(dpix), scratch.data_ptr(),
-                   g_m2.data_ptr<float>(), (float*)vp(g_col), g_op.data_ptr<float>(), g_m3.data_ptr<float>(),
-                   (float*)vp(g_cov), (float*)vp(g_sh), (float*)vp(sc_out), (float*)vp(rot_out), acc,
-                   reinterpret_cast<void*>(wait_event), (int)debug, st),
+  // the widest backward entry: no aux gradients, antialiasing or absgrad here (NULL / 0), and with
+  // split SH rows (SH colours: Inputs) colors_precomp and dL/dcolors are NULL
+  check(F.backward((int)P, (int)degree, (int)M, fp(x.bg), (int)W, (int)H, fp(x.means3D), fp(x.sh), fp(x.sh_rest),
+                   fp(x.colors), fp(x.opacity), fp(x.scales), (float)scale_modifier, fp(x.rotations), fp(x.cov3D),
+                   fp(x.view), fp(x.proj), fp(x.campos), (float)tan_fovx, (float)tan_fovy, radii.data_ptr<int>(),
+                   geom.data_ptr(), (long long)R, binning.data_ptr(), img.data_ptr(), fp(dpix), nullptr, nullptr,
+                   scratch.data_ptr(), g_m2.data_ptr<float>(), (float*)vp(g_col), g_op.data_ptr<float>(),
+                   g_m3.data_ptr<float>(), (float*)vp(g_cov), (float*)vp(g_sh), (float*)vp(sc_out), (float*)vp(rot_out),
+                   acc, reinterpret_cast<void*>(wait_event), (int)debug, st, 0, nullptr),
         "rasterize_gaussians_backward");
   return result();
 }

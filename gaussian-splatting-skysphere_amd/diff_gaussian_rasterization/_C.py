@@ -99,6 +99,29 @@ def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# Every C call below names its arguments as include/gsrast.h does (_native.ordered puts them in order),
+# and calls the widest entry of its family: the narrower ones are that entry with NULL / 0 in the
+# extra slots (csrc/gs_api.hip forwards them so).
+_call = _native.call
+
+
+def _camera(view, proj, campos, tan_fovx, tan_fovy):
+    """The camera arguments of the C entries, by name."""
+    return dict(viewmatrix=_ptr(view), projmatrix=_ptr(proj), campos=_ptr(campos), tan_fovx=float(tan_fovx),
+                tan_fovy=float(tan_fovy))
+
+
+def _aux_grads(aux_grads, H, W, dev):
+    """(dL_dout_invdepth, dL_dout_alpha) of a backward as contiguous [H, W] tensors, either may be None."""
+    if aux_grads is None:
+        return None, None
+    d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
+    for t in (d_inv, d_alpha):
+        if t is not None and t.numel() != H * W:
+            raise RuntimeError("aux gradients must have shape (1, H, W)")
+    return d_inv, d_alpha
+
+
 class _Inputs:
     """Validated, contiguous views of one rasterizer call's tensors."""
 
@@ -137,33 +160,47 @@ class _Inputs:
             if need_opacity and (self.opacity is None or self.opacity.numel() != self.P):
                 raise RuntimeError("opacities must have shape (P, 1)")
 
-    def scene(self, scale_modifier, *colour):
-        """The per-Gaussian argument group of the C entries.  colour: what the entry takes between shs
-        and opacities -- colors_precomp, features_rest (the _split entries), or both in that order."""
-        return (_ptr(self.means3D), _ptr(self.sh), *map(_ptr, colour), _ptr(self.opacity), _ptr(self.scales),
-                float(scale_modifier), _ptr(self.rotations), _ptr(self.cov3D))
+    def head(self, W, H, degree=None):
+        """The leading arguments of the C entries, by name; degree=None: an entry of the render half,
+        which takes no D / M."""
+        d = dict(P=self.P, background=_ptr(self.bg), image_width=W, image_height=H)
+        if degree is not None:
+            d.update(D=int(degree), M=self.M)
+        return d
+
+    def scene(self, scale_modifier, rest=True):
+        """The per-Gaussian arguments of the C entries, by name; rest=False: an entry without shs_rest."""
+        d = dict(means3D=_ptr(self.means3D), shs=_ptr(self.sh), colors_precomp=_ptr(self.colors),
+                 opacities=_ptr(self.opacity), scales=_ptr(self.scales), scale_modifier=float(scale_modifier),
+                 rotations=_ptr(self.rotations), cov3D_precomp=_ptr(self.cov3D))
+        if rest:
+            d["shs_rest"] = _ptr(self.sh_rest)
+        return d
 
     def camera(self, tan_fovx, tan_fovy):
-        return (_ptr(self.view), _ptr(self.proj), _ptr(self.campos), float(tan_fovx), float(tan_fovy))
+        return _camera(self.view, self.proj, self.campos, tan_fovx, tan_fovy)
 
     def preprocess(self, W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug, st,
                    antialiasing=False):
-        """The two-call forward's first half (gs_forward_preprocess; _split for split SH rows; _aa for
-        an antialiased call): (num_rendered, radii, geomBuffer), every radius written by the kernels."""
+        """The two-call forward's first half (gs_forward_preprocess_aa; gs_forward_preprocess_split for
+        split SH rows): (num_rendered, radii, geomBuffer), every radius written by the kernels."""
         radii = torch.empty((self.P,), dtype=torch.int32, device=self.device)
         geom = torch.empty((_lib.gs_geom_buffer_bytes(self.P),), dtype=torch.uint8, device=self.device)
         nr = ctypes.c_longlong(0)
         split = self.sh_rest is not None
         if antialiasing and split:
             raise RuntimeError("antialiasing: not supported with sh_split=")
-        fn = (_lib.gs_forward_preprocess_aa if antialiasing
-              else _lib.gs_forward_preprocess_split if split else _lib.gs_forward_preprocess)
-        _native.check(
-            fn(self.P, int(degree), self.M, _ptr(self.bg), W, H,
-               *self.scene(scale_modifier, self.sh_rest if split else self.colors), *self.camera(tan_fovx, tan_fovy),
-               int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(nr), int(bool(debug)), st,
-               *((1,) if antialiasing else ())),
-            "rasterize_gaussians (preprocess)")
+        args = dict(self.head(W, H, degree), **self.scene(scale_modifier, rest=split),
+                    **self.camera(tan_fovx, tan_fovy), prefiltered=int(bool(prefiltered)), radii_out=_ptr(radii),
+                    geom_buffer=_ptr(geom), debug=int(bool(debug)), stream=st)
+        if split:  # features_dc / features_rest in place of shs / colors_precomp
+            args["shs_dc"] = args.pop("shs")
+            del args["colors_precomp"]
+            _call("gs_forward_preprocess_split", "rasterize_gaussians (preprocess)", num_rendered=ctypes.byref(nr),
+                  **args)
+        else:
+            _call("gs_forward_preprocess_aa", "rasterize_gaussians (preprocess)", num_rendered_host=ctypes.byref(nr),
+                  antialiasing=int(bool(antialiasing)), **args)
         _LAST_NUM_RENDERED[0] = int(nr.value)
         return int(nr.value), radii, geom
 
@@ -209,16 +246,20 @@ def preprocess_views(backgrounds, means3D, colors, opacity, scales, rotations, s
     if capacities is not None:
         for k, c in enumerate(capacities):
             nr[k] = int(c)
-    with torch.cuda.device(dev):
-        _native.check(
-            (_lib.gs_forward_preprocess_views if capacities is None else _lib.gs_forward_preprocess_views_bounded)(
-                K, x.P, int(degree), x.M, arr([y.bg for y in xs]), (ctypes.c_int * K)(*[int(w) for w in image_widths]),
-                (ctypes.c_int * K)(*[int(h) for h in image_heights]), *x.scene(scale_modifier, x.colors),
-                arr([y.view for y in xs]), arr([y.proj for y in xs]), arr([y.campos for y in xs]),
-                (ctypes.c_float * K)(*[float(t) for t in tan_fovx]), (ctypes.c_float * K)(*[float(t) for t in tan_fovy]),
-                int(bool(prefiltered)), arr(radii), arr(geoms), nr, int(bool(debug)), _stream(dev), vst),
-            "preprocess_views")
     bounded = capacities is not None
+    # (two entries, not one family: the bounded one reads nr as the capacities and waits for nothing)
+    entry, counts = (("gs_forward_preprocess_views_bounded", "capacity") if bounded
+                     else ("gs_forward_preprocess_views", "num_rendered_host"))
+    with torch.cuda.device(dev):
+        _call(entry, "preprocess_views", K=K, P=x.P, D=int(degree), M=x.M, background=arr([y.bg for y in xs]),
+              image_width=(ctypes.c_int * K)(*[int(w) for w in image_widths]),
+              image_height=(ctypes.c_int * K)(*[int(h) for h in image_heights]),
+              **x.scene(scale_modifier, rest=False), viewmatrix=arr([y.view for y in xs]),
+              projmatrix=arr([y.proj for y in xs]), campos=arr([y.campos for y in xs]),
+              tan_fovx=(ctypes.c_float * K)(*[float(t) for t in tan_fovx]),
+              tan_fovy=(ctypes.c_float * K)(*[float(t) for t in tan_fovy]), prefiltered=int(bool(prefiltered)),
+              radii_out=arr(radii), geom_buffer=arr(geoms), debug=int(bool(debug)), stream=_stream(dev),
+              view_streams=vst, **{counts: nr})
     out = [(int(nr[k]), radii[k], geoms[k], bounded) for k in range(K)]
     W0, H0 = int(image_widths[0]), int(image_heights[0])
     if os.environ.get("GSRAST_BATCH_VIEWS", "1") != "0" and all(
@@ -232,8 +273,9 @@ def preprocess_views(backgrounds, means3D, colors, opacity, scales, rotations, s
         bins = [bin_all[k * bb:(k + 1) * bb] for k in range(K)]
         imgs = [img_all[k * ib:(k + 1) * ib] for k in range(K)]
         with torch.cuda.device(dev):
-            _native.check(_lib.gs_forward_bin_views(K, x.P, W0, H0, arr(geoms), nr, arr(bins), arr(imgs),
-                                                    int(bool(debug)), _stream(dev), vst), "preprocess_views (binning)")
+            _call("gs_forward_bin_views", "preprocess_views (binning)", K=K, P=x.P, image_width=W0, image_height=H0,
+                  geom_buffer=arr(geoms), num_rendered=nr, binning_buffer=arr(bins), image_buffer=arr(imgs),
+                  debug=int(bool(debug)), stream=_stream(dev), view_streams=vst)
         out = [(I, radii[k], geoms[k], bounded, bins[k], imgs[k]) for k in range(K)]
     if streams is not None:  # the buffers are used on the views' streams
         for k, s in enumerate(streams):
@@ -368,12 +410,10 @@ def _forward_ctypes(x, H, W, degree, scale_modifier, tan_fovx, tan_fovy, prefilt
         binning = torch.empty((_lib.gs_binning_buffer_bytes(capacity, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
         with torch.cuda.device(dev):
-            _native.check(
-                _lib.gs_forward_bounded(
-                    x.P, int(degree), x.M, _ptr(x.bg), W, H, *x.scene(scale_modifier, x.sh_rest, x.colors),
-                    *x.camera(tan_fovx, tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom), capacity,
-                    _ptr(binning), _ptr(img), _ptr(out_color), int(bool(debug)), _stream(dev)),
-                "rasterize_gaussians (bounded)")
+            _call("gs_forward_bounded", "rasterize_gaussians (bounded)", **x.head(W, H, degree),
+                  **x.scene(scale_modifier), **x.camera(tan_fovx, tan_fovy), prefiltered=int(bool(prefiltered)),
+                  radii_out=_ptr(radii), geom_buffer=_ptr(geom), capacity=capacity, binning_buffer=_ptr(binning),
+                  image_buffer=_ptr(img), out_color=_ptr(out_color), debug=int(bool(debug)), stream=_stream(dev))
         return capacity, out_color, radii, geom, binning, img
     with torch.cuda.device(dev):
         st = _stream(dev)
@@ -387,26 +427,25 @@ def _forward_ctypes(x, H, W, degree, scale_modifier, tan_fovx, tan_fovy, prefilt
                 binning, img = prepared[4], prepared[5]
                 if img.numel() != _lib.gs_image_buffer_bytes(W, H):
                     raise RuntimeError("rasterize_gaussians: the prepared view was binned for another image size")
-                _native.check(
-                    _lib.gs_forward_render_binned(
-                        x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(geom), num_rendered, _ptr(binning),
-                        _ptr(img), _ptr(out_color), int(bool(bounded)), int(bool(debug)), st),
-                    "rasterize_gaussians (render)")
+                _call("gs_forward_render_binned", "rasterize_gaussians (render)", **x.head(W, H),
+                      **x.camera(tan_fovx, tan_fovy), geom_buffer=_ptr(geom), num_rendered=num_rendered,
+                      binning_buffer=_ptr(binning), image_buffer=_ptr(img), out_color=_ptr(out_color),
+                      bounded=int(bool(bounded)), debug=int(bool(debug)), stream=st)
                 return num_rendered, out_color, radii, geom, binning, img
         else:
             num_rendered, radii, geom = x.preprocess(W, H, degree, scale_modifier, tan_fovx, tan_fovy, prefiltered,
                                                      debug, st, antialiasing=antialiasing)
         binning = torch.empty((_lib.gs_binning_buffer_bytes(num_rendered, W, H),), **u8)
         img = torch.empty((_lib.gs_image_buffer_bytes(W, H),), **u8)
-        if aux:
-            render, what = _lib.gs_forward_render_aux, "rasterize_gaussians (render, aux outputs)"
+        args = dict(x.head(W, H), **x.camera(tan_fovx, tan_fovy), radii=_ptr(radii), geom_buffer=_ptr(geom),
+                    binning_buffer=_ptr(binning), image_buffer=_ptr(img), out_color=_ptr(out_color),
+                    debug=int(bool(debug)), stream=st)
+        if bounded and not aux:  # its own mode (the sticky status), not gs_forward_render_aux's family
+            _call("gs_forward_render_bounded", "rasterize_gaussians (render)", capacity=num_rendered, **args)
         else:
-            render = _lib.gs_forward_render_bounded if bounded else _lib.gs_forward_render
-            what = "rasterize_gaussians (render)"
-        _native.check(
-            render(x.P, _ptr(x.bg), W, H, *x.camera(tan_fovx, tan_fovy), _ptr(radii), _ptr(geom), num_rendered,
-                   _ptr(binning), _ptr(img), _ptr(out_color), *map(_ptr, planes), int(bool(debug)), st),
-            what)
+            invdepth, alpha = planes or (None, None)
+            _call("gs_forward_render_aux", "rasterize_gaussians (render%s)" % (", aux outputs" if aux else ""),
+                  num_rendered=num_rendered, out_invdepth=_ptr(invdepth), out_alpha=_ptr(alpha), **args)
     return (num_rendered, out_color, radii, geom, binning, img) + planes
 
 
@@ -477,12 +516,11 @@ def contribution_stats(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmat
     R = binning_layout_count(R, binningBuffer, W, H)
     with torch.cuda.device(dev):
         scratch = torch.empty((_lib.gs_contrib_scratch_bytes(R),), dtype=torch.uint8, device=dev)
-        _native.check(
-            _lib.gs_contrib_stats(P, W, H, _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx), float(tan_fovy),
-                                  _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer),
-                                  _ptr(m), _ptr(scratch), *map(_ptr, stats), int(out is not None), int(bool(debug)),
-                                  _stream(dev)),
-            "contribution_stats")
+        _call("gs_contrib_stats", "contribution_stats", P=P, image_width=W, image_height=H,
+              **_camera(view, proj, cam, tan_fovx, tan_fovy), radii=_ptr(radii), geom_buffer=_ptr(geomBuffer),
+              num_rendered=int(R), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer),
+              pixel_weights=_ptr(m), scratch=_ptr(scratch), wsum=_ptr(stats[0]), wmax=_ptr(stats[1]),
+              count=_ptr(stats[2]), accumulate=int(out is not None), debug=int(bool(debug)), stream=_stream(dev))
     return stats
 
 
@@ -522,11 +560,10 @@ def feature_forward(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmatrix
     _, view, proj, cam = _camera_side(dev, None, viewmatrix, projmatrix, campos)
     R = binning_layout_count(R, binningBuffer, W, H) if P > 0 else 0
     with torch.cuda.device(dev):
-        _native.check(
-            _lib.gs_feature_forward(P, C, W, H, _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx), float(tan_fovy),
-                                    _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer),
-                                    _ptr(f), _ptr(out), int(bool(debug)), _stream(dev)),
-            "feature_forward")
+        _call("gs_feature_forward", "feature_forward", P=P, C=C, image_width=W, image_height=H,
+              **_camera(view, proj, cam, tan_fovx, tan_fovy), radii=_ptr(radii), geom_buffer=_ptr(geomBuffer),
+              num_rendered=int(R), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer),
+              features=_ptr(f), out=_ptr(out), debug=int(bool(debug)), stream=_stream(dev))
     return out
 
 
@@ -552,12 +589,11 @@ def feature_backward(R, radii, geomBuffer, binningBuffer, imageBuffer, viewmatri
     R = binning_layout_count(R, binningBuffer, W, H) if P > 0 else 0
     with torch.cuda.device(dev):
         scratch = torch.empty((_lib.gs_feature_scratch_bytes(R),), dtype=torch.uint8, device=dev)
-        _native.check(
-            _lib.gs_feature_backward(P, C, W, H, _ptr(view), _ptr(proj), _ptr(cam), float(tan_fovx), float(tan_fovy),
-                                     _ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer), _ptr(imageBuffer),
-                                     _ptr(g), _ptr(scratch), _ptr(grad), int(out is not None), int(bool(debug)),
-                                     _stream(dev)),
-            "feature_backward")
+        _call("gs_feature_backward", "feature_backward", P=P, C=C, image_width=W, image_height=H,
+              **_camera(view, proj, cam, tan_fovx, tan_fovy), radii=_ptr(radii), geom_buffer=_ptr(geomBuffer),
+              num_rendered=int(R), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer),
+              dL_dout=_ptr(g), scratch=_ptr(scratch), dL_dfeatures=_ptr(grad), accumulate=int(out is not None),
+              debug=int(bool(debug)), stream=_stream(dev))
     return grad
 
 
@@ -589,21 +625,21 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     (colours when SHs drive the colour, cov3D when scale/rotation drive it, ...) are None and
     not computed.  sinks: {name: (buffer, accumulate)} -- that gradient is written into (or, with
     accumulate, added to) the caller's buffer, which is returned in its place
-    (gs_backward_accumulate; multi-view gradient buckets, gs_view_parallel.GradBucket).
+    (the GS_ACC bits; multi-view gradient buckets, gs_view_parallel.GradBucket).
     wait_event: torch.cuda.Event the stream waits for before the kernel that writes the gradients
     (a sink shared with views on other streams).  sh_rest: split SH rows as rasterize_gaussians;
     the `sh` gradient is then that of the concatenation, [P, M, 3].
     aux_grads: (dL_dout_invdepth, dL_dout_alpha) of a rasterize_gaussians_aux forward, either may be
-    None (gs_backward_accumulate_aux, over ctypes).
+    None (over ctypes).
     camera: None, or whether dL/dcampos is wanted -- the return then ends with one more item, the
     view's camera gradients (dL_dviewmatrix [4, 4], dL_dprojmatrix [4, 4], dL_dcampos [3] or None) of
-    gs_backward_camera, run right behind the backward on its stream (over ctypes).
+    gs_backward_camera_aa, run right behind the backward on its stream (over ctypes).
     aa_opacity: the opacities [P, 1] of a rasterize_gaussians_aa forward -- the backward of an antialiased
-    view (gs_backward_accumulate_aa / gs_backward_camera_aa, over ctypes), which chains through the
-    opacity scale and so reads them; None: a plain forward's backward.
+    view (over ctypes), which chains through the opacity scale and so reads them; None: a plain
+    forward's backward.
     absgrad: the return ends with one more item (after the camera gradients), the view's absolute
-    screen-space gradient [P, 3] (gs_backward_accumulate_absgrad, over ctypes; with sh_rest, aux_grads,
-    camera and aa_opacity as above)."""
+    screen-space gradient [P, 3] (over ctypes; with sh_rest, aux_grads, camera and aa_opacity as above).
+    Every combination is one call of gs_backward_accumulate_absgrad, the widest entry of its family."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None
     antialiasing = aa_opacity is not None
@@ -631,8 +667,9 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     has_sr = x.scales is not None and x.rotations is not None and x.cov3D is None
     shapes = dict(means2D=(P, 3), colors=(P, 3), opacity=(P, 1), means3D=(P, 3), cov3D=(P, 6), sh=(P, M, 3),
                   scales=(P, 3), rotations=(P, 4))
-    # is the gradient computed by the kernels (else zero-filled or absent)?
-    computed = dict(means2D=True, colors=True, opacity=True, means3D=True,
+    # is the gradient computed by the kernels (else zero-filled or absent)?  Split SH rows are SH colours
+    # (no colors_precomp: _Inputs): dL/dcolors is not asked of the library, and with want_all it is zeros
+    computed = dict(means2D=True, colors=x.sh_rest is None, opacity=True, means3D=True,
                     cov3D=x.cov3D is not None or (want_all and has_sr), sh=x.sh is not None, scales=has_sr,
                     rotations=has_sr)
     needed = dict(means2D=True, colors=need_col, opacity=True, means3D=True, cov3D=need_cov, sh=need_sh,
@@ -663,127 +700,75 @@ def backward_impl(background, means3D, radii, colors, scales, rotations, scale_m
     if P == 0:
         return ret
     dpix = _f32(dL_dout_color, "dL_dout_color", dev)
-    o = {n: (outs[n] if computed[n] else None) for n in GRAD_NAMES}
+    grads = {"dL_d" + n: _ptr(outs[n] if computed[n] else None) for n in GRAD_NAMES}
     R = binning_layout_count(R, binningBuffer, W, H)
     with torch.cuda.device(dev):
         st = _stream(dev)
-        wait = ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None
-        # the argument groups every variant shares; the calls differ in the colour sources, the aux
-        # gradients in front of the scratch and (split SH rows: SH colours) the dL/dcolors output
-        head = (P, int(degree), M, _ptr(x.bg), W, H)
-        bufs = x.camera(tan_fovx, tan_fovy) + (_ptr(radii), _ptr(geomBuffer), int(R), _ptr(binningBuffer),
-                                               _ptr(imageBuffer), _ptr(dpix))
-        grads = [_ptr(o[n]) for n in GRAD_NAMES]
-        tail = (acc, wait, int(bool(debug)), st)
-        what = "rasterize_gaussians_backward"
-        d_inv = d_alpha = None
-        n_scratch = _lib.gs_grad_buffer_bytes(R)
-        if aux_grads is not None:
-            d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
-            for t in (d_inv, d_alpha):
-                if t is not None and t.numel() != H * W:
-                    raise RuntimeError("aux gradients must have shape (1, H, W)")
-            n_scratch = _lib.gs_grad_buffer_bytes_aux(R, P)
-            what += " (aux outputs)"
+        d_inv, d_alpha = _aux_grads(aux_grads, H, W, dev)
+        what = "rasterize_gaussians_backward" + (" (aux outputs)" if aux_grads is not None else "")
         if absgrad:
             n_scratch = _lib.gs_grad_buffer_bytes_absgrad(R, P)
-        grad_scratch = torch.empty((n_scratch,), dtype=torch.uint8, device=dev)
-        if absgrad:
-            rc = _lib.gs_backward_accumulate_absgrad(
-                *head, *x.scene(scale_modifier, None if antialiasing else x.sh_rest, x.colors), *bufs, _ptr(d_inv),
-                _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail, int(antialiasing), _ptr(abs_out))
             what += " (antialiasing, absgrad)" if antialiasing else " (absgrad)"
-        elif antialiasing:
-            rc = _lib.gs_backward_accumulate_aa(*head, *x.scene(scale_modifier, None, x.colors), *bufs, _ptr(d_inv),
-                                                _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail, 1)
-            what += " (antialiasing)"
-        elif aux_grads is not None:
-            rc = _lib.gs_backward_accumulate_aux(*head, *x.scene(scale_modifier, x.sh_rest, x.colors), *bufs,
-                                                 _ptr(d_inv), _ptr(d_alpha), _ptr(grad_scratch), *grads, *tail)
         else:
-            if x.sh_rest is not None:
-                rc = _lib.gs_backward_accumulate_split(*head, *x.scene(scale_modifier, x.sh_rest), *bufs,
-                                                       _ptr(grad_scratch), grads[0], *grads[2:], *tail)
-            else:
-                rc = _lib.gs_backward_accumulate(*head, *x.scene(scale_modifier, x.colors), *bufs, _ptr(grad_scratch),
-                                                 *grads, *tail)
-        _native.check(rc, what)
+            n_scratch = _lib.gs_grad_buffer_bytes(R) if aux_grads is None else _lib.gs_grad_buffer_bytes_aux(R, P)
+            what += " (antialiasing)" if antialiasing else ""
+        grad_scratch = torch.empty((n_scratch,), dtype=torch.uint8, device=dev)
+        _call("gs_backward_accumulate_absgrad", what, **x.head(W, H, degree), **x.scene(scale_modifier),
+              **x.camera(tan_fovx, tan_fovy), radii=_ptr(radii), geom_buffer=_ptr(geomBuffer), num_rendered=int(R),
+              binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), dL_dout_color=_ptr(dpix),
+              dL_dout_invdepth=_ptr(d_inv), dL_dout_alpha=_ptr(d_alpha), grad_buffer=_ptr(grad_scratch),
+              **grads, accumulate=acc,
+              wait_event=ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None,
+              debug=int(bool(debug)), stream=st, antialiasing=int(antialiasing), dL_dmeans2D_abs=_ptr(abs_out))
         if camera is not None:
             cam_scratch = torch.empty((_lib.gs_camera_grad_scratch_bytes(P),), dtype=torch.uint8, device=dev)
-            cam_fn = _lib.gs_backward_camera_aa if antialiasing else _lib.gs_backward_camera
-            rc = cam_fn(*head, *x.scene(scale_modifier, x.colors), *x.camera(tan_fovx, tan_fovy),
-                        _ptr(geomBuffer), int(R), _ptr(grad_scratch) if aux_grads is not None else None,
-                        int(aux_grads is not None), _ptr(cam_scratch), _ptr(cam_out),
-                        ctypes.c_void_p(cam_out.data_ptr() + 64),
-                        ctypes.c_void_p(cam_out.data_ptr() + 128) if camera else None,
-                        int(bool(debug)), st, *((1,) if antialiasing else ()))
-            _native.check(rc, "rasterize_gaussians_backward (camera gradients)")
+            _call("gs_backward_camera_aa", "rasterize_gaussians_backward (camera gradients)", **x.head(W, H, degree),
+                  **x.scene(scale_modifier, rest=False), **x.camera(tan_fovx, tan_fovy), geom_buffer=_ptr(geomBuffer),
+                  num_rendered=int(R), aux_grad_buffer=_ptr(grad_scratch) if aux_grads is not None else None,
+                  aux_valid=int(aux_grads is not None), scratch=_ptr(cam_scratch), dL_dviewmatrix=_ptr(cam_out),
+                  dL_dprojmatrix=ctypes.c_void_p(cam_out.data_ptr() + 64),
+                  dL_dcampos=ctypes.c_void_p(cam_out.data_ptr() + 128) if camera else None, debug=int(bool(debug)),
+                  stream=st, antialiasing=int(antialiasing))
     return ret
 
 
 def backward_render(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, dL_dout_color, P, degree, M,
                     geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug, aux_grads=None):
-    """Per-tile half of the backward (gs_backward_render): the view's per-Gaussian record sums,
+    """Per-tile half of the backward (gs_backward_render_aux): the view's per-Gaussian record sums,
     kept in geomBuffer for backward_gaussians, and its dL_dmeans2D [P, 3] (or None).
     aux_grads: (dL_dout_invdepth, dL_dout_alpha) of a rasterize_gaussians_aux forward, either may be
-    None (gs_backward_render_aux, over ctypes); the return is then (dL_dmeans2D, invdepth_sums): the
+    None (over ctypes); the return is then (dL_dmeans2D, invdepth_sums): the
     [P] per-Gaussian dL/d(1 / z) sums of the depth chain (written for Gaussians with instances only),
     the input of FusedAdam.prepare_fused_backward."""
     if aux_grads is not None and aux_grads[0] is None and aux_grads[1] is None:
         aux_grads = None
-    if aux_grads is not None:
-        return _backward_render_aux(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, dL_dout_color,
-                                    P, degree, M, geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug,
-                                    aux_grads)
-    if _EXT is not None and geomBuffer.is_cuda:
+    aux = aux_grads is not None
+    if not aux and _EXT is not None and geomBuffer.is_cuda:
         return _EXT.backward_render(background, viewmatrix, projmatrix, campos, float(tan_fovx), float(tan_fovy),
                                     dL_dout_color, int(P), int(degree), int(M), geomBuffer, int(R), binningBuffer,
                                     imageBuffer, bool(want_means2D), bool(debug))
     dev = geomBuffer.device
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     dm2 = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_means2D else None
+    sums = torch.empty((P,), dtype=torch.float32, device=dev) if aux else None
+    ret = (dm2, sums) if aux else dm2
     if P == 0:
-        return dm2
+        return ret
     bg, view, proj, cam = _camera_side(dev, background, viewmatrix, projmatrix, campos)
     dpix = _f32(dL_dout_color, "dL_dout_color", dev)
+    d_inv, d_alpha = _aux_grads(aux_grads, H, W, dev)
     R = binning_layout_count(R, binningBuffer, W, H)
     with torch.cuda.device(dev):
-        st = _stream(dev)
-        grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes(R),), dtype=torch.uint8, device=dev)
-        _native.check(
-            _lib.gs_backward_render(P, int(degree), int(M), _ptr(bg), W, H, _ptr(view), _ptr(proj), _ptr(cam),
-                                    float(tan_fovx), float(tan_fovy), _ptr(geomBuffer), int(R), _ptr(binningBuffer),
-                                    _ptr(imageBuffer), _ptr(dpix), _ptr(grad_scratch), _ptr(dm2), 0,
-                                    int(bool(debug)), st),
-            "rasterize_gaussians_backward (render half)")
-    return dm2
-
-
-def _backward_render_aux(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, dL_dout_color, P, degree, M,
-                         geomBuffer, R, binningBuffer, imageBuffer, want_means2D, debug, aux_grads):
-    dev = geomBuffer.device
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    dm2 = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_means2D else None
-    sums = torch.empty((P,), dtype=torch.float32, device=dev)
-    if P == 0:
-        return dm2, sums
-    bg, view, proj, cam = _camera_side(dev, background, viewmatrix, projmatrix, campos)
-    dpix = _f32(dL_dout_color, "dL_dout_color", dev)
-    d_inv, d_alpha = (_f32(t, n, dev) for t, n in zip(aux_grads, ("dL_dout_invdepth", "dL_dout_alpha")))
-    for t in (d_inv, d_alpha):
-        if t is not None and t.numel() != H * W:
-            raise RuntimeError("aux gradients must have shape (1, H, W)")
-    R = binning_layout_count(R, binningBuffer, W, H)
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        grad_scratch = torch.empty((_lib.gs_grad_buffer_bytes_aux(R, P),), dtype=torch.uint8, device=dev)
-        _native.check(
-            _lib.gs_backward_render_aux(P, int(degree), int(M), _ptr(bg), W, H, _ptr(view), _ptr(proj), _ptr(cam),
-                                        float(tan_fovx), float(tan_fovy), _ptr(geomBuffer), int(R),
-                                        _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix), _ptr(d_inv), _ptr(d_alpha),
-                                        _ptr(grad_scratch), _ptr(dm2), _ptr(sums), 0, int(bool(debug)), st),
-            "rasterize_gaussians_backward (render half, aux outputs)")
-    return dm2, sums
+        n_scratch = _lib.gs_grad_buffer_bytes_aux(R, P) if aux else _lib.gs_grad_buffer_bytes(R)
+        grad_scratch = torch.empty((n_scratch,), dtype=torch.uint8, device=dev)
+        what = "rasterize_gaussians_backward (render half%s)" % (", aux outputs" if aux else "")
+        _call("gs_backward_render_aux", what, P=P, D=int(degree), M=int(M), background=_ptr(bg), image_width=W,
+              image_height=H, **_camera(view, proj, cam, tan_fovx, tan_fovy), geom_buffer=_ptr(geomBuffer),
+              num_rendered=int(R), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer),
+              dL_dout_color=_ptr(dpix), dL_dout_invdepth=_ptr(d_inv), dL_dout_alpha=_ptr(d_alpha),
+              grad_buffer=_ptr(grad_scratch), dL_dmeans2D=_ptr(dm2), invdepth_sums=_ptr(sums), accumulate=0,
+              debug=int(bool(debug)), stream=_stream(dev))
+    return ret
 
 
 def backward_gaussians(means3D, sh, colors, scales, rotations, cov3D_precomp, scale_modifier, degree, views, outs,
@@ -816,15 +801,15 @@ def backward_gaussians(means3D, sh, colors, scales, rotations, cov3D_precomp, sc
             raise RuntimeError(f"backward_gaussians: {n} output must be a contiguous float32 tensor on {dev}")
     count = P - int(first) if count is None else int(count)
     with torch.cuda.device(dev):
-        _native.check(
-            _lib.gs_backward_gaussians_range(
-                P, int(first), count, int(degree), x.M, _ptr(x.means3D), _ptr(x.sh), _ptr(x.colors), _ptr(x.scales),
-                float(scale_modifier), _ptr(x.rotations), _ptr(x.cov3D), len(views), arr, _ptr(o["colors"]),
-                _ptr(o["opacity"]), _ptr(o["means3D"]), _ptr(o["cov3D"]), _ptr(o["sh"]), _ptr(o["scales"]),
-                _ptr(o["rotations"]), int(accumulate),
-                ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None, int(bool(debug)),
-                _stream(dev)),
-            "rasterize_gaussians_backward (per-Gaussian half)")
+        _call("gs_backward_gaussians_range", "rasterize_gaussians_backward (per-Gaussian half)", P=P, first=int(first),
+              count=count, D=int(degree), M=x.M, means3D=_ptr(x.means3D), shs=_ptr(x.sh),
+              colors_precomp=_ptr(x.colors), scales=_ptr(x.scales), scale_modifier=float(scale_modifier),
+              rotations=_ptr(x.rotations), cov3D_precomp=_ptr(x.cov3D), num_views=len(views), views=arr,
+              dL_dcolors=_ptr(o["colors"]), dL_dopacity=_ptr(o["opacity"]), dL_dmeans3D=_ptr(o["means3D"]),
+              dL_dcov3D=_ptr(o["cov3D"]), dL_dsh=_ptr(o["sh"]), dL_dscales=_ptr(o["scales"]),
+              dL_drotations=_ptr(o["rotations"]), accumulate=int(accumulate),
+              wait_event=ctypes.c_void_p(wait_event.cuda_event) if wait_event is not None else None,
+              debug=int(bool(debug)), stream=_stream(dev))
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -870,12 +855,10 @@ def debug_export(P, W, H, num_rendered, geomBuffer, binningBuffer, imageBuffer, 
     )
     if P > 0:
         with torch.cuda.device(device):
-            _native.check(
-                _lib.gs_debug_export(P, W, H, L, _ptr(geomBuffer), _ptr(binningBuffer),
-                                     _ptr(imageBuffer), *[_ptr(out[k]) for k in (
-                                         "point_list", "ranges", "xy", "conic_opacity", "rgb", "depth",
-                                         "tiles_touched", "final_T", "n_contrib")], _stream(device)),
-                "debug_export")
+            # (the outputs carry the entry's parameter names)
+            _call("gs_debug_export", "debug_export", P=P, image_width=W, image_height=H, num_rendered=L,
+                  geom_buffer=_ptr(geomBuffer), binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer),
+                  stream=_stream(device), **{k: _ptr(t) for k, t in out.items()})
     out["point_list"] = out["point_list"][:num_rendered]
     return out
 
@@ -888,6 +871,7 @@ def debug_export_slots(W, H, num_rendered, binningBuffer, imageBuffer, device):
     slots = torch.zeros((max(L, 1),), dtype=torch.int32, device=device)
     cuts = torch.zeros((gx * gy,), dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _native.check(_lib.gs_debug_export_slots(W, H, L, _ptr(binningBuffer), _ptr(imageBuffer),
-                                                 _ptr(slots), _ptr(cuts), _stream(device)), "debug_export_slots")
+        _call("gs_debug_export_slots", "debug_export_slots", image_width=W, image_height=H, num_rendered=L,
+              binning_buffer=_ptr(binningBuffer), image_buffer=_ptr(imageBuffer), slots=_ptr(slots),
+              tile_cut=_ptr(cuts), stream=_stream(device))
     return slots[:int(num_rendered)], cuts

@@ -193,9 +193,11 @@ class FusedAdam(torch.optim.Optimizer):
                 modes = (ctypes.c_int * n)(*[x[7] for x in it])
                 cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
                 with torch.cuda.device(dev):
-                    _native.check(_lib.gs_adam_step_activated(
-                        n, cast(P), cast(G), cast(modes), int(sh_coeffs), cast(M), cast(V), cast(numel), cast(lr),
-                        cast(steps), cast(wd), b1, b2, eps, int(maximize), st), "adam step (activated)")
+                    _native.call("gs_adam_step_activated", "adam step (activated)", count=n, params_host=cast(P),
+                                 grad_src_host=cast(G), grad_mode_host=cast(modes), sh_coeffs=int(sh_coeffs),
+                                 exp_avg_host=cast(M), exp_avg_sq_host=cast(V), numel_host=cast(numel),
+                                 lr_host=cast(lr), step_host=cast(steps), weight_decay_host=cast(wd), beta1=b1,
+                                 beta2=b2, eps=eps, maximize=int(maximize), stream=st)
 
     def _checked_state(self, p):
         """(exp_avg, exp_avg_sq) of p, created if absent, checked dense fp32 of p's size (a state
@@ -288,9 +290,10 @@ class FusedAdam(torch.optim.Optimizer):
             _check_densify_stats(max_r, accum, denom, radii, vgrad)
             if radii.shape[0] != P:
                 raise ValueError(f"step_fused_backward: statistics of {radii.shape[0]} Gaussians, expected {P}")
-            stat_args = [_ptr(radii), _ptr(vgrad), vgrad.shape[1], _ptr(max_r), _ptr(accum), _ptr(denom)]
+            stat_args = dict(radii=_ptr(radii), grad2d=_ptr(vgrad), grad_stride=vgrad.shape[1], max_radii2D=_ptr(max_r),
+                             grad_accum=_ptr(accum), denom=_ptr(denom))
         else:
-            stat_args = [None, None, 0, None, None, None]
+            stat_args = dict(radii=None, grad2d=None, grad_stride=0, max_radii2D=None, grad_accum=None, denom=None)
         sums = inputs.get("invdepth_sums")
         if sums is not None:
             _check_f32_dense(sums, "FusedAdam invdepth_sums")
@@ -299,14 +302,18 @@ class FusedAdam(torch.optim.Optimizer):
                                  f"expected ({P},) on {dev}")
         arr = lambda ts: ctypes.cast((ctypes.c_void_p * 6)(*[t.data_ptr() for t in ts]), ctypes.c_void_p)  # noqa: E731
         steps_c = (ctypes.c_longlong * 6)()
-        args = [P, int(inputs["degree"]), 16, _ptr(xyz), _ptr(dc), _ptr(rest), _ptr(scales),
-                float(inputs["scale_modifier"]), _ptr(rots), ctypes.byref(vg), arr(params), arr(ms), arr(vs),
-                ctypes.cast((ctypes.c_double * 6)(*lrs), ctypes.c_void_p), ctypes.cast(steps_c, ctypes.c_void_p),
-                ctypes.cast((ctypes.c_double * 6)(*wds), ctypes.c_void_p), b1, b2, eps, int(maximize), *stat_args,
-                *([] if sums is None else [_ptr(sums)]), int(bool(inputs.get("debug", False))),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)]
+        # the widest entry of its family: without statistics / inverse-depth sums their pointers are NULL
+        args = _native.ordered(
+            "gs_backward_gaussians_adam_stats_aux", P=P, D=int(inputs["degree"]), M=16, means3D=_ptr(xyz),
+            shs_dc=_ptr(dc), shs_rest=_ptr(rest), scales=_ptr(scales), scale_modifier=float(inputs["scale_modifier"]),
+            rotations=_ptr(rots), view=ctypes.byref(vg), params_host=arr(params), exp_avg_host=arr(ms),
+            exp_avg_sq_host=arr(vs), lr_host=ctypes.cast((ctypes.c_double * 6)(*lrs), ctypes.c_void_p),
+            step_host=ctypes.cast(steps_c, ctypes.c_void_p),
+            weight_decay_host=ctypes.cast((ctypes.c_double * 6)(*wds), ctypes.c_void_p), beta1=b1, beta2=b2, eps=eps,
+            maximize=int(maximize), **stat_args, invdepth_sums=_ptr(sums), debug=int(bool(inputs.get("debug", False))),
+            stream=ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         keep = (vm, pm, cp, geom, vg, inputs, stats, sums)  # alive until the launch
-        entry = _lib.gs_backward_gaussians_adam_stats if sums is None else _lib.gs_backward_gaussians_adam_stats_aux
+        entry = _lib.gs_backward_gaussians_adam_stats_aux
 
         def launch(defer_commit: bool = False):
             """Advances the step counts and launches.  defer_commit: launches with the next step
@@ -340,8 +347,10 @@ class FusedAdam(torch.optim.Optimizer):
         wd = (ctypes.c_double * n)(*[it[6] for it in items])
         cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
         with torch.cuda.device(dev):
-            _native.check(_lib.gs_adam_step(n, cast(P), cast(G), cast(M), cast(V), cast(numel), cast(lr),
-                                            cast(steps), cast(wd), b1, b2, eps, int(maximize), st), "adam step")
+            _native.call("gs_adam_step", "adam step", count=n, params_host=cast(P), grads_host=cast(G),
+                         exp_avg_host=cast(M), exp_avg_sq_host=cast(V), numel_host=cast(numel), lr_host=cast(lr),
+                         step_host=cast(steps), weight_decay_host=cast(wd), beta1=b1, beta2=b2, eps=eps,
+                         maximize=int(maximize), stream=st)
 
 
 def densify_stats(max_radii2D: torch.Tensor, grad_accum: torch.Tensor, denom: torch.Tensor, radii: torch.Tensor,
@@ -436,6 +445,11 @@ def row_chunks(P: int, waits):
     return out
 
 
+# gs_activate_forward's input and output parameters (include/gsrast.h)
+_ACT_IN = ("features_dc", "features_rest", "opacity_raw", "scaling_raw", "rotation_raw")
+_ACT_OUT = ("shs", "opacity", "scales", "rotations")
+
+
 class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, with_sh=True, row_waits=None,
@@ -477,7 +491,8 @@ class _Activate(torch.autograd.Function):
                         pi = [ctypes.c_void_p(t.data_ptr() + 4 * lo * w) for t, w in zip(ins5, widths_in)]
                         po = [None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * lo * w)
                               for t, w in zip(outs, widths_out)]
-                        _native.check(_lib.gs_activate_forward(hi - lo, 3 * K, *pi, *po, st), "activate (row chunk)")
+                        _native.call("gs_activate_forward", "activate (row chunk)", P=hi - lo, sh_rest=3 * K,
+                                     **dict(zip(_ACT_IN, pi)), **dict(zip(_ACT_OUT, po)), stream=st)
                     done = torch.cuda.Event()
                     done.record(side)
                     if waits_out is not None:
@@ -496,9 +511,9 @@ class _Activate(torch.autograd.Function):
         else:
             st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             with torch.cuda.device(dev):
-                _native.check(_lib.gs_activate_forward(P, 3 * K, _ptr(dc), _ptr(rest), _ptr(o), _ptr(s), _ptr(q),
-                                                       _ptr(shs), _ptr(opac), _ptr(scales), _ptr(rots), st),
-                              "activate")
+                _native.call("gs_activate_forward", "activate", P=P, sh_rest=3 * K, features_dc=_ptr(dc),
+                             features_rest=_ptr(rest), opacity_raw=_ptr(o), scaling_raw=_ptr(s), rotation_raw=_ptr(q),
+                             shs=_ptr(shs), opacity=_ptr(opac), scales=_ptr(scales), rotations=_ptr(rots), stream=st)
         ctx.P, ctx.K = P, K
         ctx.shapes = (tuple(f_dc.shape), tuple(f_rest.shape), tuple(opacity_raw.shape))
         ctx.set_materialize_grads(False)
@@ -523,10 +538,11 @@ class _Activate(torch.autograd.Function):
         if any(t is not None for t in (dshs, dopac, dscales, drots)):
             st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             with torch.cuda.device(dev):
-                _native.check(_lib.gs_activate_backward(P, 3 * K, _ptr(dshs), _ptr(dopac), _ptr(dscales),
-                                                        _ptr(drots), _ptr(opac), _ptr(scales), _ptr(q), _ptr(g_dc),
-                                                        _ptr(g_rest), _ptr(g_o), _ptr(g_s), _ptr(g_q), st),
-                              "activate backward")
+                _native.call("gs_activate_backward", "activate backward", P=P, sh_rest=3 * K, dL_dshs=_ptr(dshs),
+                             dL_dopacity=_ptr(dopac), dL_dscales=_ptr(dscales), dL_drotations=_ptr(drots),
+                             opacity=_ptr(opac), scales=_ptr(scales), rotation_raw=_ptr(q), dL_dfeatures_dc=_ptr(g_dc),
+                             dL_dfeatures_rest=_ptr(g_rest), dL_dopacity_raw=_ptr(g_o), dL_dscaling_raw=_ptr(g_s),
+                             dL_drotation_raw=_ptr(g_q), stream=st)
         return g_dc, g_rest, g_o, g_s, g_q, None, None, None
 
 
@@ -615,11 +631,12 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size,
     totals = torch.empty((4,), dtype=torch.int32, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
-        _native.check(_lib.gs_densify_classify(
-            P, _ptr(accum), _ptr(denom), _ptr(src[3]), _ptr(src[4]), float(max_grad),
-            float(gaussians.percent_dense * extent), float(min_opacity), float(0.1 * extent),
-            1 if max_screen_size else 0, float(max_screen_size) if max_screen_size else 0.0, int(N),
-            _ptr(flags), _ptr(counts), _ptr(totals), st), "densify classify")
+        _native.call("gs_densify_classify", "densify classify", P=P, grad_accum=_ptr(accum), denom=_ptr(denom),
+                     opacity_raw=_ptr(src[3]), scaling_raw=_ptr(src[4]), grad_threshold=float(max_grad),
+                     pd_extent=float(gaussians.percent_dense * extent), min_opacity=float(min_opacity),
+                     big_extent=float(0.1 * extent), has_screen=1 if max_screen_size else 0,
+                     max_screen=float(max_screen_size) if max_screen_size else 0.0, N=int(N), flags=_ptr(flags),
+                     block_counts=_ptr(counts), totals=_ptr(totals), stream=st)
         tot = [int(v) for v in totals.cpu()]  # the one host read: sizes of the new tensors
         tot_h = (ctypes.c_uint32 * 4)(*tot)
         n_split = tot[2]
@@ -656,13 +673,12 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size,
                 v_in.append(None)
                 m_out.append(None)
                 v_out.append(None)
-        arr = lambda ts: (ctypes.c_void_p * 6)(*[_ptr(x) for x in ts])  # noqa: E731
-        _native.check(_lib.gs_densify_emit(
-            P, N, tot_h, _ptr(flags), _ptr(counts), _ptr(samples) if n_split else None,
-            ctypes.cast(arr(src), ctypes.c_void_p), ctypes.cast(arr(m_in), ctypes.c_void_p),
-            ctypes.cast(arr(v_in), ctypes.c_void_p), ctypes.cast(arr(outs), ctypes.c_void_p),
-            ctypes.cast(arr(m_out), ctypes.c_void_p), ctypes.cast(arr(v_out), ctypes.c_void_p),
-            ctypes.cast((ctypes.c_int * 6)(*widths), ctypes.c_void_p), st), "densify emit")
+        arr = lambda ts: ctypes.cast((ctypes.c_void_p * 6)(*[_ptr(x) for x in ts]), ctypes.c_void_p)  # noqa: E731
+        _native.call("gs_densify_emit", "densify emit", P=P, N=N, totals_host=tot_h, flags=_ptr(flags),
+                     block_counts=_ptr(counts), samples=_ptr(samples) if n_split else None, params_host=arr(src),
+                     exp_avg_host=arr(m_in), exp_avg_sq_host=arr(v_in), out_params_host=arr(outs),
+                     out_exp_avg_host=arr(m_out), out_exp_avg_sq_host=arr(v_out),
+                     widths_host=ctypes.cast((ctypes.c_int * 6)(*widths), ctypes.c_void_p), stream=st)
     # gradient buckets (gs_view_parallel.GradBucket) that own the old parameters' gradients
     from diff_gaussian_rasterization import _sink_owner
 
