@@ -50,25 +50,22 @@ def quat_R(q):
     ], -2)
 
 
-def _prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, shs=None, deg=0, colors=None,
-          scales=None, rots=None, cov3D=None, mod=1.0):
-    """The per-Gaussian half (projection, EWA covariance, conic, radius, colour, tile rectangle)."""
-    dt = means3D.dtype
-    P = means3D.shape[0]
-    ones = torch.ones((P, 1), dtype=dt, device=means3D.device)
+def _sigma(scales, rots, cov3D, mod):
+    if cov3D is None:
+        L = quat_R(rots) * (mod * scales)[:, None, :]
+        return L @ L.transpose(1, 2)
+    c = cov3D
+    return torch.stack([torch.stack([c[:, 0], c[:, 1], c[:, 2]], -1), torch.stack([c[:, 1], c[:, 3], c[:, 4]], -1),
+                        torch.stack([c[:, 2], c[:, 4], c[:, 5]], -1)], -2)
+
+
+def raw_cov2(means3D, view, tanfovx, tanfovy, W, H, scales=None, rots=None, cov3D=None, mod=1.0):
+    """-> (ph [P, 4] homogeneous means, p_view [P, 4], tz [P], cov2 [P, 2, 2]): the EWA covariance before
+    the 0.3 dilation."""
+    ones = torch.ones((means3D.shape[0], 1), dtype=means3D.dtype, device=means3D.device)
     ph = torch.cat([means3D, ones], 1)
     p_view = ph @ view
-    p_hom = ph @ proj
-    p_w = 1.0 / (p_hom[:, 3:4] + 1e-7)
-    ndc = p_hom[:, :2] * p_w + means2D[:, :2]
-    if cov3D is None:
-        R = quat_R(rots)
-        L = R * (mod * scales)[:, None, :]
-        Sig = L @ L.transpose(1, 2)
-    else:
-        c = cov3D
-        Sig = torch.stack([torch.stack([c[:, 0], c[:, 1], c[:, 2]], -1), torch.stack([c[:, 1], c[:, 3], c[:, 4]], -1),
-                           torch.stack([c[:, 2], c[:, 4], c[:, 5]], -1)], -2)
+    Sig = _sigma(scales, rots, cov3D, mod)
     fx, fy = W / (2 * tanfovx), H / (2 * tanfovy)
     tz = p_view[:, 2]
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
@@ -82,9 +79,18 @@ def _prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, sh
     zero = torch.zeros_like(tz)
     J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / tz ** 2], -1),
                      torch.stack([zero, fy / tz, -fy * ty / tz ** 2], -1)], -2)
-    Rw = view[:3, :3].T
-    T = J @ Rw
-    cov2 = T @ Sig @ T.transpose(1, 2)
+    T = J @ view[:3, :3].T
+    return ph, p_view, tz, T @ Sig @ T.transpose(1, 2)
+
+
+def _prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, shs=None, deg=0, colors=None,
+          scales=None, rots=None, cov3D=None, mod=1.0):
+    """The per-Gaussian half (projection, EWA covariance, conic, radius, colour, tile rectangle)."""
+    dt = means3D.dtype
+    ph, p_view, tz, cov2 = raw_cov2(means3D, view, tanfovx, tanfovy, W, H, scales, rots, cov3D, mod)
+    p_hom = ph @ proj
+    p_w = 1.0 / (p_hom[:, 3:4] + 1e-7)
+    ndc = p_hom[:, :2] * p_w + means2D[:, :2]
     a, b, c = cov2[:, 0, 0] + 0.3, cov2[:, 0, 1], cov2[:, 1, 1] + 0.3
     det = a * c - b * b
     conic = torch.stack([c / det, -b / det, a / det], -1)
@@ -111,7 +117,9 @@ def _prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, sh
         radii = torch.where(visible, radius, torch.zeros_like(radius)).to(torch.int32)
         srt = torch.argsort(tz, stable=True)
         order = srt[visible[srt]].tolist()
-    return dict(pix=pix, conic=conic, rgb=rgb, tz=tz, x0=x0, y0=y0, x1=x1, y1=y1, radii=radii, order=order)
+        rect = torch.stack([x0, y0, x1, y1], 1).to(torch.int64).cpu()
+    return dict(pix=pix, conic=conic, rgb=rgb, tz=tz, x0=x0, y0=y0, x1=x1, y1=y1, radii=radii, order=order, rect=rect,
+                opac=opac, W=W, H=H)
 
 
 def render(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, bg, shs=None, deg=0, colors=None,
@@ -148,6 +156,75 @@ def render(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, b
     return img.reshape(3, H, W), radii
 
 
+
+
+def rect_pixels(r, W, H, dev):
+    """(yy, xx) int64 grids of the pixels of a tile rectangle (x0, y0, x1, y1), clipped to the image."""
+    rx0, ry0, rx1, ry1 = (int(v) for v in r)
+    xs = torch.arange(16 * rx0, min(16 * rx1, W), device=dev)
+    ys = torch.arange(16 * ry0, min(16 * ry1, H), device=dev)
+    return torch.meshgrid(ys, xs, indexing="ij")
+
+
+class walk_local:
+    """The front-to-back walk over the dict `q` of _prep, Gaussian by Gaussian over the pixels of its
+    tile rectangle.  Iterating yields, per Gaussian of q["order"],
+
+        (i, idx, dx, dy, a_raw, alpha, Ti, ok)
+
+    idx: the flat pixel indices of the rectangle; dx, dy = mean2D_i - p; a_raw = o G; alpha = min(0.99, a_raw);
+    Ti: the transmittance in front of i; ok: i is composited there (the pixel live, power <= 0,
+    alpha >= 1/255, and not the entry that stops the pixel at T < 1e-4).  The walk keeps T, the stopped
+    pixels `done` and the `flag` map (see render_local); `T`, `done` and `flag` (flat, [H W]) are final once it
+    is exhausted.
+    T is updated when the consumer asks for the next Gaussian, after its own accumulation.
+
+    graph=True  (the autograd references): alpha is the straight-through a_raw - clamp(a_raw.detach() - 0.99, 0),
+                the decisions are taken under no_grad and T is updated functionally;
+    graph=False (the no_grad references): alpha = clamp(a_raw, max=0.99) and T is updated in place.
+    The two alphas are not the same floats above 0.99."""
+
+    def __init__(self, q, graph, flag_rel=1e-5, flag_T_rel=None):
+        self.q, self.graph = q, graph
+        self.flag_rel, self.flag_T_rel = flag_rel, flag_rel if flag_T_rel is None else flag_T_rel
+        dt, dev, npx = q["pix"].dtype, q["pix"].device, q["W"] * q["H"]
+        self.T = torch.ones(npx, dtype=dt, device=dev)
+        self.flag = torch.zeros(npx, dtype=torch.bool, device=dev)
+        self.done = torch.zeros(npx, dtype=torch.bool, device=dev)
+
+    def __iter__(self):
+        q, flag_rel, flag_T_rel = self.q, self.flag_rel, self.flag_T_rel
+        pix, conic, opac, W, H = q["pix"], q["conic"], q["opac"], q["W"], q["H"]
+        dt, dev = pix.dtype, pix.device
+        done = self.done
+        for i in q["order"]:
+            yy, xx = rect_pixels(q["rect"][i], W, H, dev)
+            idx = (yy * W + xx).reshape(-1)
+            dx, dy = pix[i, 0] - xx.reshape(-1).to(dt), pix[i, 1] - yy.reshape(-1).to(dt)
+            power = -0.5 * (conic[i, 0] * dx * dx + conic[i, 2] * dy * dy) - conic[i, 1] * dx * dy
+            a_raw = opac[i] * torch.exp(power)
+            if self.graph:
+                alpha = a_raw - torch.clamp(a_raw.detach() - 0.99, min=0.0)
+            else:
+                alpha = torch.clamp(a_raw, max=0.99)
+            Ti = self.T[idx]
+            with torch.no_grad():
+                live = ~done[idx]
+                ok = live & (power <= 0) & (alpha >= 1.0 / 255.0)
+                test_T = Ti * (1 - alpha)
+                stop = ok & (test_T < 1e-4)
+                near = live & (((alpha - 1.0 / 255.0).abs() <= flag_rel / 255.0) | (power.abs() <= 1e-6)
+                               | (ok & ((test_T - 1e-4).abs() <= flag_T_rel * 1e-4)))
+                self.flag[idx] |= near
+                ok = ok & ~stop
+                done[idx] |= stop
+            yield i, idx, dx, dy, a_raw, alpha, Ti, ok
+            if self.graph:
+                self.T = self.T.index_put((idx,), torch.where(ok, Ti * (1 - alpha), Ti))
+            else:
+                self.T[idx] = torch.where(ok, test_T, Ti)
+
+
 def render_local(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, bg, shs=None, deg=0,
                  colors=None, scales=None, rots=None, cov3D=None, mod=1.0, flag_rel=1e-5, flag_T_rel=None):
     """The same function as render(), composited Gaussian by Gaussian over the pixels of its tile
@@ -155,41 +232,11 @@ def render_local(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W
     Gaussians.  Also returns a bool [H, W] map of the pixels where some tested decision lies within
     `flag_rel` (relative) of its threshold -- alpha vs 1/255, the tested T vs 1e-4 (`flag_T_rel`
     if given) -- or power within 1e-6 of 0: there an fp32 evaluation may decide the other way."""
-    flag_T_rel = flag_rel if flag_T_rel is None else flag_T_rel
-    dt, dev = means3D.dtype, means3D.device
     q = _prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, shs, deg, colors, scales, rots,
               cov3D, mod)
-    pix, conic, rgb, x0, y0, x1, y1, radii, order = (q[k] for k in ("pix", "conic", "rgb", "x0", "y0", "x1", "y1",
-                                                                     "radii", "order"))
-    npx = W * H
-    Tr = torch.ones(npx, dtype=dt, device=dev)
-    C = torch.zeros((3, npx), dtype=dt, device=dev)
-    done = torch.zeros(npx, dtype=torch.bool, device=dev)
-    flag = torch.zeros(npx, dtype=torch.bool, device=dev)
-    rect = torch.stack([x0, y0, x1, y1], 1).to(torch.int64).cpu()
-    for i in order:
-        rx0, ry0, rx1, ry1 = (int(v) for v in rect[i])
-        xs = torch.arange(16 * rx0, min(16 * rx1, W), device=dev)
-        ys = torch.arange(16 * ry0, min(16 * ry1, H), device=dev)
-        yy, xx = torch.meshgrid(ys, xs, indexing="ij")
-        idx = (yy * W + xx).reshape(-1)
-        dx, dy = pix[i, 0] - xx.reshape(-1).to(dt), pix[i, 1] - yy.reshape(-1).to(dt)
-        power = -0.5 * (conic[i, 0] * dx * dx + conic[i, 2] * dy * dy) - conic[i, 1] * dx * dy
-        a_raw = opac[i] * torch.exp(power)
-        alpha = a_raw - torch.clamp(a_raw.detach() - 0.99, min=0.0)   # min(0.99, .), straight-through grad
-        Ti = Tr[idx]
-        with torch.no_grad():
-            live = ~done[idx]
-            ok = live & (power <= 0) & (alpha >= 1.0 / 255.0)
-            test_T = Ti * (1 - alpha)
-            stop = ok & (test_T < 1e-4)
-            near = live & (((alpha - 1.0 / 255.0).abs() <= flag_rel / 255.0) | (power.abs() <= 1e-6)
-                           | (ok & ((test_T - 1e-4).abs() <= flag_T_rel * 1e-4)))
-            flag[idx] |= near
-            ok = ok & ~stop
-            done[idx] |= stop
-        okf = ok.to(dt)
-        C = C.index_add(1, idx, rgb[i][:, None] * (alpha * Ti * okf)[None])
-        Tr = Tr.index_put((idx,), torch.where(ok, Ti * (1 - alpha), Ti))
-    img = C + Tr[None] * bg[:, None]
-    return img.reshape(3, H, W), radii, flag.reshape(H, W)
+    walk = walk_local(q, True, flag_rel, flag_T_rel)
+    C = torch.zeros((3, W * H), dtype=means3D.dtype, device=means3D.device)
+    for i, idx, _, _, _, alpha, Ti, ok in walk:
+        C = C.index_add(1, idx, q["rgb"][i][:, None] * (alpha * Ti * ok.to(C.dtype))[None])
+    img = C + walk.T[None] * bg[:, None]
+    return img.reshape(3, H, W), q["radii"], walk.flag.reshape(H, W)

@@ -1,7 +1,7 @@
 """Dense reference of the absolute screen-space gradient (test infrastructure).
 
-absgrad_local restates dense_ref.render_local's loop -- the same _prep, the same decisions, the same `flag`
-map with flag_rel / flag_T_rel as dense_ref_contrib -- in two passes and without autograd:
+absgrad_local consumes dense_ref.walk_local -- the same _prep, the same decisions, the same `flag` map with
+flag_rel / flag_T_rel as dense_ref.render_local -- in two passes and without autograd:
 
   front to back  each Gaussian i keeps its pixels, d = mean2D_i - p, o G, alpha = min(0.99, o G), the
                  transmittance T_i in front of it and `ok` (composited: inside the tile rectangle, the pixel
@@ -37,41 +37,14 @@ def absgrad_local(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, 
     """-> dict(abs [P, 3], signed [P, 3] (input dtype), radii [P] int32, flag [H, W] bool, keep [H, W] bool,
     rect [P, 4] int64 (x0, y0, x1, y1 in tiles)).  dL_dimage [3, H, W]; dL_dalpha /
     dL_dinvdepth [H, W] or [1, H, W] or None."""
-    flag_T_rel = flag_rel if flag_T_rel is None else flag_T_rel
     dt, dev = means3D.dtype, means3D.device
     P = means3D.shape[0]
     q = dense_ref._prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, shs, deg, colors, scales,
                         rots, cov3D, mod)
-    pix, conic, rgb, tz, x0, y0, x1, y1, radii, order = (q[k] for k in ("pix", "conic", "rgb", "tz", "x0", "y0", "x1",
-                                                                         "y1", "radii", "order"))
-    npx = W * H
-    Tr = torch.ones(npx, dtype=dt, device=dev)
-    done = torch.zeros(npx, dtype=torch.bool, device=dev)
-    flag = torch.zeros(npx, dtype=torch.bool, device=dev)
-    rect = torch.stack([x0, y0, x1, y1], 1).to(torch.int64).cpu()
-    kept = []
-    for i in order:
-        rx0, ry0, rx1, ry1 = (int(v) for v in rect[i])
-        xs = torch.arange(16 * rx0, min(16 * rx1, W), device=dev)
-        ys = torch.arange(16 * ry0, min(16 * ry1, H), device=dev)
-        yy, xx = torch.meshgrid(ys, xs, indexing="ij")
-        idx = (yy * W + xx).reshape(-1)
-        dx, dy = pix[i, 0] - xx.reshape(-1).to(dt), pix[i, 1] - yy.reshape(-1).to(dt)
-        power = -0.5 * (conic[i, 0] * dx * dx + conic[i, 2] * dy * dy) - conic[i, 1] * dx * dy
-        a_raw = opac[i] * torch.exp(power)
-        alpha = torch.clamp(a_raw, max=0.99)
-        Ti = Tr[idx]
-        live = ~done[idx]
-        ok = live & (power <= 0) & (alpha >= 1.0 / 255.0)
-        test_T = Ti * (1 - alpha)
-        stop = ok & (test_T < 1e-4)
-        near = live & (((alpha - 1.0 / 255.0).abs() <= flag_rel / 255.0) | (power.abs() <= 1e-6)
-                       | (ok & ((test_T - 1e-4).abs() <= flag_T_rel * 1e-4)))
-        flag[idx] |= near
-        ok = ok & ~stop
-        done[idx] |= stop
-        kept.append((i, idx, dx, dy, a_raw, alpha, Ti, ok))
-        Tr[idx] = torch.where(ok, test_T, Ti)
+    conic, rgb, tz = q["conic"], q["rgb"], q["tz"]
+    walk = dense_ref.walk_local(q, False, flag_rel, flag_T_rel)
+    kept = list(walk)
+    npx, flag, Tr = W * H, walk.flag, walk.T
 
     keep = torch.ones(npx, dtype=torch.bool, device=dev)
     if zero_flagged:
@@ -99,7 +72,8 @@ def absgrad_local(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, 
         out_sgn[i, 0] = -0.5 * W * (qq * bx).sum()
         out_sgn[i, 1] = -0.5 * H * (qq * by).sum()
         S[idx] += gc * (alpha * Ti) * okf
-    return dict(abs=out_abs, signed=out_sgn, radii=radii, flag=flag.reshape(H, W), keep=keep.reshape(H, W), rect=rect)
+    return dict(abs=out_abs, signed=out_sgn, radii=q["radii"], flag=flag.reshape(H, W), keep=keep.reshape(H, W),
+                rect=q["rect"])
 
 
 @torch.no_grad()
@@ -112,17 +86,13 @@ def half_planes(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W,
     q = dense_ref._prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, shs, deg, colors, scales,
                         rots, cov3D, mod)
     pix, conic = q["pix"], q["conic"]
-    rect = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu()
-    owner = torch.zeros((H, W), dtype=torch.int64)
+    owner = torch.zeros((H, W), dtype=torch.int64, device=dev)
     hx = torch.zeros((H, W), dtype=torch.bool, device=dev)
     hy = torch.zeros((H, W), dtype=torch.bool, device=dev)
     for i in q["order"]:
-        rx0, ry0, rx1, ry1 = (int(v) for v in rect[i])
-        ys, xs = slice(16 * ry0, min(16 * ry1, H)), slice(16 * rx0, min(16 * rx1, W))
-        owner[ys, xs] += 1
-        yy, xx = torch.meshgrid(torch.arange(ys.start, ys.stop, device=dev), torch.arange(xs.start, xs.stop, device=dev),
-                                indexing="ij")
+        yy, xx = dense_ref.rect_pixels(q["rect"][i], W, H, dev)
+        owner[yy, xx] += 1
         dx, dy = pix[i, 0] - xx.to(dt), pix[i, 1] - yy.to(dt)
-        hx[ys, xs] = conic[i, 0] * dx + conic[i, 1] * dy > 0
-        hy[ys, xs] = conic[i, 1] * dx + conic[i, 2] * dy > 0
+        hx[yy, xx] = conic[i, 0] * dx + conic[i, 1] * dy > 0
+        hy[yy, xx] = conic[i, 1] * dx + conic[i, 2] * dy > 0
     return dict(x=hx, y=hy, overlap=bool((owner > 1).any()), radii=q["radii"])

@@ -1,9 +1,9 @@
 """Dense reference of feature rendering and its gradient in the features (test infrastructure).
 
-features_local restates dense_ref_contrib.contributions_local's loop -- the same _prep, the same
-decisions, the same `flag` map with flag_rel / flag_T_rel -- with C channels in the input dtype.
-With w_i(p) = alpha_i(p) T_i(p) over the pixels where Gaussian i is composited (`ok` of the colour
-loop, the entry that stops a pixel excluded),
+features_local consumes dense_ref.walk_local -- the same _prep, the same decisions, the same `flag` map
+with flag_rel / flag_T_rel as dense_ref_contrib.contributions_local -- with C channels in the input dtype.
+With w_i(p) = alpha_i(p) T_i(p) over the pixels where Gaussian i is composited (`ok` of the walk,
+the entry that stops a pixel excluded),
 
     out[c, p]   = sum_i f_i[c] w_i(p)               front to back, no background term
     dfeat[i, c] = sum_p w_i(p) g_c(p)               for a given image gradient g [C, H, W]
@@ -25,45 +25,21 @@ def features_local(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy,
                    zero_flagged=False, also_flag=None):
     """-> dict(out [C, H, W], dfeat [P, C] (input dtype; None without g), flag [H, W] bool,
     radii [P] int32, g [C, H, W] as used).  features: [P, C]; also_flag: bool [H, W] or None."""
-    flag_T_rel = flag_rel if flag_T_rel is None else flag_T_rel
     dt, dev = means3D.dtype, means3D.device
     P = means3D.shape[0]
     f = features.to(dev, dt)
     C = f.shape[1]
     q = dense_ref._prep(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy, W, H, shs, deg, colors, scales,
                         rots, cov3D, mod)
-    pix, conic, x0, y0, x1, y1, radii, order = (q[k] for k in ("pix", "conic", "x0", "y0", "x1", "y1", "radii",
-                                                                "order"))
+    walk = dense_ref.walk_local(q, False, flag_rel, flag_T_rel)
     npx = W * H
-    Tr = torch.ones(npx, dtype=dt, device=dev)
-    done = torch.zeros(npx, dtype=torch.bool, device=dev)
-    flag = torch.zeros(npx, dtype=torch.bool, device=dev)
     out = torch.zeros((C, npx), dtype=dt, device=dev)
-    rect = torch.stack([x0, y0, x1, y1], 1).to(torch.int64).cpu()
     kept = []
-    for i in order:
-        rx0, ry0, rx1, ry1 = (int(v) for v in rect[i])
-        xs = torch.arange(16 * rx0, min(16 * rx1, W), device=dev)
-        ys = torch.arange(16 * ry0, min(16 * ry1, H), device=dev)
-        yy, xx = torch.meshgrid(ys, xs, indexing="ij")
-        idx = (yy * W + xx).reshape(-1)
-        dx, dy = pix[i, 0] - xx.reshape(-1).to(dt), pix[i, 1] - yy.reshape(-1).to(dt)
-        power = -0.5 * (conic[i, 0] * dx * dx + conic[i, 2] * dy * dy) - conic[i, 1] * dx * dy
-        alpha = torch.clamp(opac[i] * torch.exp(power), max=0.99)
-        Ti = Tr[idx]
-        live = ~done[idx]
-        ok = live & (power <= 0) & (alpha >= 1.0 / 255.0)
-        test_T = Ti * (1 - alpha)
-        stop = ok & (test_T < 1e-4)
-        near = live & (((alpha - 1.0 / 255.0).abs() <= flag_rel / 255.0) | (power.abs() <= 1e-6)
-                       | (ok & ((test_T - 1e-4).abs() <= flag_T_rel * 1e-4)))
-        flag[idx] |= near
-        ok = ok & ~stop
-        done[idx] |= stop
+    for i, idx, _, _, _, alpha, Ti, ok in walk:
         w = (alpha * Ti) * ok.to(dt)
         out[:, idx] += f[i][:, None] * w[None, :]
         kept.append((i, idx, w))
-        Tr[idx] = torch.where(ok, test_T, Ti)
+    flag = walk.flag
     dfeat, gg = None, None
     if g is not None:
         gg = g.to(dev, dt).reshape(C, npx)
@@ -74,4 +50,4 @@ def features_local(means3D, means2D, opac, view, proj, campos, tanfovx, tanfovy,
         for i, idx, w in kept:
             dfeat[i] = gg[:, idx] @ w
         gg = gg.reshape(C, H, W)
-    return dict(out=out.reshape(C, H, W), dfeat=dfeat, flag=flag.reshape(H, W), radii=radii, g=gg)
+    return dict(out=out.reshape(C, H, W), dfeat=dfeat, flag=flag.reshape(H, W), radii=q["radii"], g=gg)

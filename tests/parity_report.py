@@ -1,7 +1,7 @@
 """Measured parity errors of the GPU tests (DESIGN.md §0 / §2 contract table).
 
-With GS_PARITY_REPORT=<path> set, every tolerance check of tests/test_gpu_parity.py and
-tests/test_gpu_dense.py appends one JSON line: the test, the tensor, the bound it asserts
+With GS_PARITY_REPORT=<path> set, every tolerance check of the GPU tests (tests/gpu_checks.py and the
+few rules that stay in their files) appends one JSON line: the test, the tensor, the bound it asserts
 (|d| <= rtol |ref| + frac max|ref|), the measured max|d| / max|ref| and the largest fraction of the
 bound used anywhere (`used` <= 1 passes).  tools/parity_table.py reduces the file to the table."""
 import json

@@ -19,37 +19,20 @@ whose fp64 ratio r lies within 1e-3 (relative) of the floor 2.5e-5, where fp32 m
 branch of the chain gradient.  The counts are bounded: 2 %, 0.1 %, 1 %."""
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import dense_cases
 import dense_ref
 import dense_ref_aa
 import dense_ref_aux
+import gpu_checks
 import gs_scenes
-import parity_report
+from gpu_checks import check_4x, exact_mode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
 EYE, TARGET = (0.7, -0.4, -1.1), (0.1, 0.2, 4.0)
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture
-def exact():
-    prev = _lib().gs_set_exact_exp(1)
-    yield
-    _lib().gs_set_exact_exp(prev)
-
-
-def _np(x):
-    return x.detach().double().cpu().numpy()
 
 
 def _cov6(d):
@@ -186,30 +169,12 @@ def _masks(name, sc, device, radii, aux=False):
                                 math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), W, H, shs=ref.get("shs"),
                                 deg=sc["deg"], colors=ref.get("colors"), scales=ref.get("scales"),
                                 rots=ref.get("rotations"), cov3D=ref.get("cov3D"), mod=sc["mod"])
-        rect = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-        for i in np.nonzero(rdiff)[0]:
-            x0, y0, x1, y1 = rect[i]
-            fl[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+        dense_cases.wide_mask(q["rect"].numpy(), rdiff, W, H, into=fl)
     at_floor = int((r <= dense_ref_aa.AA_FLOOR).sum())
     print(f"\n[aa {name}] flagged pixels {int(fl.sum())}/{fl.size}, radii differing {int(rdiff.sum())}/{P}, "
           f"near the floor {int(near_floor.sum())}/{P}, at s = 0.005 {at_floor}/{P}, visible {int((radii > 0).sum())}")
     assert fl.mean() <= 0.02 and rdiff.mean() <= 1e-3 and near_floor.mean() <= 0.01
     return fl, ~rdiff & ~near_floor
-
-
-def _check_4x(got, ref, f32, name, keep=None):
-    """max|hip - f64| <= 4 max|dense f32 - f64| + 1e-5 max|f64|"""
-    g, r, n = _np(got), _np(ref), _np(f32)
-    if keep is not None:
-        g, r, n = g[keep], r[keep], n[keep]
-    d_gpu, d_32, scale = np.abs(g - r).max(initial=0.0), np.abs(n - r).max(initial=0.0), np.abs(r).max(initial=0.0)
-    bound = 4.0 * d_32 + RTOL * scale
-    if scale > 0:
-        parity_report.record(name, g, r, 0.0, bound / scale)
-    print(f"  {name}: max|hip - f64| {d_gpu:.3e}  max|dense f32 - f64| {d_32:.3e}  max|f64| {scale:.3e}  "
-          f"(hip {d_gpu / scale if scale else 0.0:.2e}, dense f32 {d_32 / scale if scale else 0.0:.2e} of max; "
-          f"{d_gpu / bound if bound > 0 else 0.0:.2f} of the bound)")
-    assert d_gpu <= bound, (name, d_gpu, d_32, scale)
 
 
 def _against_dense(name, device, aux=False, cam_leaves=False):
@@ -233,10 +198,10 @@ def _against_dense(name, device, aux=False, cam_leaves=False):
         runs[dtype] = (rt, rcams, routs)
     (r64, c64, o64), (r32, c32, o32) = runs[torch.float64], runs[torch.float32]
     for k, nm in enumerate(("image", "invdepth", "alpha")[:len(outs)]):
-        _check_4x(outs[k].permute(1, 2, 0), o64[k].permute(1, 2, 0), o32[k].permute(1, 2, 0), f"{nm} [aa {name}]", ~fl)
+        check_4x(outs[k].permute(1, 2, 0), o64[k].permute(1, 2, 0), o32[k].permute(1, 2, 0), f"{nm} [aa {name}]", ~fl)
     zero = lambda x: torch.zeros_like(x) if x.grad is None else x.grad  # noqa: E731
     for k in t:
-        _check_4x(zero(t[k]), zero(r64[k]), zero(r32[k]), f"d{k} [aa {name}]", keep_g)
+        check_4x(zero(t[k]), zero(r64[k]), zero(r32[k]), f"d{k} [aa {name}]", keep_g)
     assert float(zero(r64["opacities"]).abs().max()) > 0
     return sc, t, cams, (c64, c32), zero
 
@@ -250,7 +215,7 @@ def test_off_is_off(device):
     sc = _scene("off", device)
     s, _ = _settings(sc, device)
     w = _weights(sc, device)[0]
-    lib = _lib()
+    lib = gpu_checks.lib()
 
     def run(**kw):
         t = _fresh(sc["leaves"])
@@ -282,7 +247,7 @@ def test_off_is_off(device):
 # ------------------------------------------------------------------------------------------
 # 2. the render path is untouched
 # ------------------------------------------------------------------------------------------
-def test_equals_the_plain_call_with_the_effective_opacities(device, exact):
+def test_equals_the_plain_call_with_the_effective_opacities(device, exact_mode):
     from diff_gaussian_rasterization import _C
 
     cam = gs_scenes.identity_camera(192, 128)
@@ -366,7 +331,7 @@ def test_aux_alpha_is_one_minus_final_T(device):
 def test_camera_gradients(device, name):
     sc, t, cams, (c64, c32), zero = _against_dense(name, device, cam_leaves=True)
     for k, nm in enumerate(("viewmatrix", "projmatrix", "campos")):
-        _check_4x(zero(cams[k]), zero(c64[k]), zero(c32[k]), f"d{nm} [aa {name}]")
+        check_4x(zero(cams[k]), zero(c64[k]), zero(c32[k]), f"d{nm} [aa {name}]")
     assert float(zero(c64[0]).abs().max()) > 0
     if name != "cam2":
         return

@@ -40,52 +40,14 @@ import numpy as np
 import pytest
 import torch
 
-import dense_ref
+import dense_cases
 import dense_ref_aa
 import dense_ref_absgrad
+import gpu_checks
 import gs_scenes
-import parity_report
+from gpu_checks import RTOL, check_4x, check_tol, mode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-5
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture(params=[1, 0], ids=["exact", "fast"])
-def mode(request):
-    """Both numerics modes (the save / restore idiom of tests/test_gpu_parity.py)."""
-    prev = _lib().gs_set_exact_exp(request.param)
-    yield request.param
-    _lib().gs_set_exact_exp(prev)
-
-
-_SCENES = {}
-
-
-def _scene(name, device):
-    """(cam, leaves, sh degree) of a named scene; built once."""
-    if name not in _SCENES:
-        cam = gs_scenes.identity_camera(200, 120)
-        if name in ("sparse", "empty-tile"):
-            sc, deg = gs_scenes.random_gaussians(2000, 3, cam=cam, seed=41), 3
-        elif name == "deep":
-            sc, deg = gs_scenes.random_gaussians(6000, 1, cam=cam, seed=47, scale_range=(0.01, 0.08)), 1
-        else:
-            sc, deg = gs_scenes.random_gaussians(8000, 1, cam=cam, seed=49, scale_range=(0.02, 0.12)), 1
-            sc.opacities = 0.5 + 0.49 * sc.opacities
-        leaves = {k: getattr(sc, k) for k in ("means3D", "opacities", "shs", "scales", "rotations")}
-        if name == "empty-tile":
-            leaves = {k: v[:3].contiguous() for k, v in leaves.items()}
-            cam = gs_scenes.identity_camera(72, 40)
-        _SCENES[name] = (cam, {k: v.to(device) for k, v in leaves.items()}, deg)
-    return _SCENES[name]
-
 
 def _dpix(cam, device, seed=5):
     """a random signed dL/dimage of unit scale"""
@@ -177,7 +139,7 @@ def _backward_raw(entry, s, leaves, fwd, dpix, aux_grads, device, want_abs=True,
     before the call).  -> (the eight gradients, absgrad or None, the launch names)."""
     from diff_gaussian_rasterization import _C
 
-    lib = _lib()
+    lib = gpu_checks.lib()
     R, _, radii, geom, binning, img = fwd[:6]
     P, M = leaves["means3D"].shape[0], leaves["shs"].shape[1]
     H, W = s.image_height, s.image_width
@@ -229,7 +191,7 @@ def _backward_raw(entry, s, leaves, fwd, dpix, aux_grads, device, want_abs=True,
 def test_bit_identities(device, mode, name):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     dpix, ag = _dpix(cam, device), _aux_grads(cam, device)
@@ -319,19 +281,9 @@ def _check_ge(ab, grad, name):
         assert np.all(short <= tol), f"{name}[{k}]: {int((short > tol).sum())} below |grad| - tol"
 
 
-def _check2(got, ref, name):
-    """|got - ref| <= 2 (1e-5 |ref| + 1e-5 max|ref|)"""
-    got, ref = got.detach().double().cpu().numpy(), ref.detach().double().cpu().numpy()
-    d, tol = np.abs(got - ref), _tol2(ref)
-    parity_report.record(name, got, ref, 2 * RTOL, 2 * RTOL)
-    print(f"{name}: max|d| {d.max(initial=0.0):.3e}  max|ref| {np.abs(ref).max(initial=0.0):.3e}  "
-          f"({float((d / np.maximum(tol, 1e-300)).max(initial=0.0)):.3f} of the bound)")
-    assert np.all(d <= tol), f"{name}: {int((d > tol).sum())}/{d.size} beyond tol, max|d| {d.max():.3e}"
-
-
 @pytest.mark.parametrize("name", ["sparse", "deep", "opaque"])
 def test_triangle_inequality(device, mode, name):
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     print()
     r = _run(cam, leaves, deg, device, _dpix(cam, device), True)
     _check_ge(r["absgrad"], r["grads"][1], f"[{name}]")
@@ -362,17 +314,12 @@ def _grid_scene(device):
     return cam, {k: v.float().contiguous().to(device) for k, v in leaves.items()}, cols.to(device)
 
 
-def _ref_args(cam, device, dt):
-    return (cam.world_view_transform.to(device, dt), cam.full_proj_transform.to(device, dt),
-            cam.camera_center.to(device, dt), math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), cam.image_width,
-            cam.image_height)
-
-
 def test_one_signed_terms_equal_the_signed_gradient(device, mode):
     cam, leaves, cols = _grid_scene(device)
     H, W = cam.image_height, cam.image_width
     hp = dense_ref_absgrad.half_planes(leaves["means3D"], torch.zeros_like(leaves["means3D"]), leaves["opacities"],
-                                       *_ref_args(cam, device, torch.float32), colors=cols, scales=leaves["scales"],
+                                       *dense_cases.dense_args(cam, device, torch.float32), colors=cols,
+                                       scales=leaves["scales"],
                                        rots=leaves["rotations"])
     assert not hp["overlap"], "the splats' tile rectangles must not overlap"
     assert int((hp["radii"] > 0).sum()) == 12
@@ -385,7 +332,7 @@ def test_one_signed_terms_equal_the_signed_gradient(device, mode):
         assert torch.equal(r["radii"].cpu(), hp["radii"].cpu())
         ab, gr = r["absgrad"][:, k], r["grads"][1][:, k]
         assert float(gr.abs().min()) > 0
-        _check2(ab, gr.abs(), f"one-signed {side}: absgrad vs |grad|")
+        check_tol(ab, gr.abs(), f"one-signed {side}: absgrad vs |grad|", times=2)
         # (the other column's terms change sign inside the half-plane: it stays a strict bound somewhere)
         _check_ge(r["absgrad"], r["grads"][1], f"one-signed {side}")
 
@@ -435,7 +382,7 @@ def _dense(cam, leaves, deg, device, dt, dpix, ag, **flags):
     t = {k: v.detach().to(dt) for k, v in leaves.items()}
     bg = torch.zeros(3, dtype=dt, device=device)
     return dense_ref_absgrad.absgrad_local(
-        t["means3D"], torch.zeros_like(t["means3D"]), t["opacities"], *_ref_args(cam, device, dt), bg, dpix.to(dt),
+        t["means3D"], t["means2D"], t["opacities"], *dense_cases.dense_args(cam, device, dt), bg, dpix.to(dt),
         shs=t["shs"], deg=deg, scales=t["scales"], rots=t["rotations"],
         dL_dalpha=None if ag is None else ag[1].to(dt), dL_dinvdepth=None if ag is None else ag[0].to(dt), **flags)
 
@@ -446,18 +393,10 @@ def _dense_case(key, cam, leaves, deg, device, hip_radii, dpix, ag):
     c = _DENSE.setdefault(key, {})
     if "probe" not in c:
         # (radii and rectangles do not depend on the gradient)
-        f = torch.float64
-        q = dense_ref._prep(leaves["means3D"].to(f), torch.zeros_like(leaves["means3D"], dtype=f),
-                            leaves["opacities"].to(f), *_ref_args(cam, device, f), shs=leaves["shs"].to(f), deg=deg,
-                            scales=leaves["scales"].to(f), rots=leaves["rotations"].to(f))
-        c["rect"] = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-        c["radii"] = q["radii"].cpu()
+        c["rect"], c["radii"] = dense_cases.rect_and_radii(cam, leaves, deg, device)
         c["probe"] = True
     rdiff = (hip_radii.cpu() != c["radii"]).numpy()
-    wide = np.zeros((cam.image_height, cam.image_width), bool)
-    for i in np.nonzero(rdiff)[0]:
-        x0, y0, x1, y1 = c["rect"][i]
-        wide[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+    wide = dense_cases.wide_mask(c["rect"], rdiff, cam.image_width, cam.image_height)
     if "wide" not in c or not np.array_equal(c["wide"], wide):
         c["wide"] = wide
         c["f64"] = _dense(cam, leaves, deg, device, torch.float64, dpix, ag, flag_rel=1e-3, flag_T_rel=1e-2,
@@ -470,20 +409,9 @@ def _dense_case(key, cam, leaves, deg, device, hip_radii, dpix, ag):
     return c["dpix"], c["ag"], fl, rdiff, c["f64"], c["f32"]
 
 
-def _check_4x(got, ref, f32, name, keep):
-    """the conditioning rule: max|hip - f64| <= 4 max|dense f32 - f64| + 1e-5 max|f64|"""
-    g, r, n = (x.detach().double().cpu().numpy()[keep] for x in (got, ref, f32))
-    d_gpu, d_32, scale = np.abs(g - r).max(initial=0.0), np.abs(n - r).max(initial=0.0), np.abs(r).max(initial=0.0)
-    bound = 4.0 * d_32 + RTOL * scale
-    parity_report.record(name, g, r, 0.0, bound / scale if scale > 0 else 0.0)
-    print(f"  {name}: max|hip - f64| {d_gpu:.3e}  max|dense f32 - f64| {d_32:.3e}  max|f64| {scale:.3e}  "
-          f"({d_gpu / bound if bound > 0 else 0.0:.2f} of the bound)")
-    assert scale > 0 and d_gpu <= bound, (name, d_gpu, d_32, scale)
-
-
 @pytest.mark.parametrize("name,aux", [("sparse", False), ("deep", False), ("opaque", False), ("sparse", True)])
 def test_against_dense_fp64(device, mode, name, aux):
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     P = leaves["means3D"].shape[0]
     dpix0, ag0 = _dpix(cam, device, seed=17), (_aux_grads(cam, device, seed=18) if aux else None)
     radii = _run(cam, leaves, deg, device, dpix0, False)["radii"]
@@ -495,8 +423,9 @@ def test_against_dense_fp64(device, mode, name, aux):
     r = _run(cam, leaves, deg, device, dpix, True, aux_grads=ag)
     keep = ~rdiff
     for k in range(2):
-        _check_4x(r["absgrad"][:, k], r64["abs"][:, k], r32["abs"][:, k], f"[{name}{'+aux' if aux else ''}] absgrad[{k}]",
-                  keep)
+        assert float(r64["abs"][:, k][torch.from_numpy(keep)].abs().max()) > 0
+        check_4x(r["absgrad"][:, k], r64["abs"][:, k], r32["abs"][:, k], f"[{name}{'+aux' if aux else ''}] absgrad[{k}]",
+                 keep)
     assert not r["absgrad"][:, 2].any()
 
 
@@ -506,7 +435,7 @@ def test_against_dense_fp64(device, mode, name, aux):
 def test_antialiasing_equals_the_plain_call_with_the_compensated_opacities(device, mode):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = _scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     dpix = _dpix(cam, device)
@@ -539,7 +468,7 @@ def test_antialiasing_equals_the_plain_call_with_the_compensated_opacities(devic
     assert torch.equal(aa["radii"], plain["radii"])
     print()
     for k in range(2):
-        _check2(aa["absgrad"][:, k], plain["absgrad"][:, k], f"antialiased absgrad[{k}] vs compensated opacities")
+        check_tol(aa["absgrad"][:, k], plain["absgrad"][:, k], f"antialiased absgrad[{k}] vs compensated opacities", times=2)
 
 
 # ------------------------------------------------------------------------------------------
@@ -565,7 +494,7 @@ def _snapshot(m):
 def test_add_densification_stats(device, mode):
     import gs_train
 
-    cam, leaves, deg = _scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     P = leaves["means3D"].shape[0]
     r = _run(cam, leaves, deg, device, _dpix(cam, device), True)
 
@@ -644,7 +573,7 @@ def test_autograd_refusals(device):
     import gs_view_parallel
     from diff_gaussian_rasterization import GaussianRasterizer, prepare_views
 
-    cam, leaves, deg = _scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     r = GaussianRasterizer(gs_scenes.raster_settings_for(cam, deg, device=device))
     kw = dict(means3D=leaves["means3D"], opacities=leaves["opacities"], shs=leaves["shs"], scales=leaves["scales"],
               rotations=leaves["rotations"])

@@ -43,61 +43,21 @@ and the two small aux kernels are launched in this process (tests/test_zz_kernel
    relative drift does not cancel with the terms), with the dense fp32 run at 0.80 elsewhere.
 4. Interface: the refused combinations, an accumulating gradient sink, P == 0, single aux gradients.
 """
-import math
-
-import numpy as np
 import pytest
 import torch
 
-import dense_ref
+import dense_cases
 import dense_ref_aux
 import gs_scenes
 import parity_report
+import gpu_checks
+from gpu_checks import RTOL, check_4x, check_tol, mode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
 CHAIN = ("means2D", "means3D", "scales", "rotations")
 LEAVES = ("means3D", "means2D", "opacities", "shs", "scales", "rotations")
 AUX_KERNELS = ("render_fwd_aux", "render_bwd_aux", "sum_records_aux", "depth_chain_aux")
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture(params=[1, 0], ids=["exact", "fast"])
-def mode(request):
-    """Both numerics modes (the save / restore idiom of tests/test_gpu_parity.py)."""
-    prev = _lib().gs_set_exact_exp(request.param)
-    yield request.param
-    _lib().gs_set_exact_exp(prev)
-
-
-_SCENES = {}
-
-
-def _scene(name, device):
-    """(cam, leaves, sh degree) of a named scene; built once."""
-    if name not in _SCENES:
-        cam = gs_scenes.identity_camera(200, 120)
-        if name in ("sparse", "empty-tile"):
-            sc, deg = gs_scenes.random_gaussians(2000, 3, cam=cam, seed=41), 3
-        elif name == "deep":
-            sc, deg = gs_scenes.random_gaussians(6000, 1, cam=cam, seed=47, scale_range=(0.01, 0.08)), 1
-        else:
-            sc, deg = gs_scenes.random_gaussians(8000, 1, cam=cam, seed=49, scale_range=(0.02, 0.12)), 1
-            sc.opacities = 0.5 + 0.49 * sc.opacities
-        leaves = {k: getattr(sc, k) for k in ("means3D", "opacities", "shs", "scales", "rotations")}
-        if name == "empty-tile":
-            leaves = {k: v[:3].contiguous() for k, v in leaves.items()}
-            cam = gs_scenes.identity_camera(72, 40)
-        leaves = {k: v.to(device) for k, v in leaves.items()}
-        leaves["means2D"] = torch.zeros_like(leaves["means3D"])
-        _SCENES[name] = (cam, leaves, deg)
-    return _SCENES[name]
 
 
 def _weights(cam, device, seed=5):
@@ -157,10 +117,10 @@ def _raw_aux(cam, leaves, deg, device):
 def test_bit_identities(device, mode, name):
     from diff_gaussian_rasterization import _native
 
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     gC, gD, gA = _weights(cam, device)
     (img0, radii0), t0 = _hip(cam, leaves, deg, device, aux=False, gC=gC)
-    lib = _lib()
+    lib = gpu_checks.lib()
     # the per-name launch log of one aux forward's colour-only backward
     from diff_gaussian_rasterization import GaussianRasterizer
 
@@ -212,21 +172,9 @@ def test_bit_identities(device, mode, name):
 # ------------------------------------------------------------------------------------------
 # 2. against the existing colour path
 # ------------------------------------------------------------------------------------------
-def _check2(got, ref, name, frac):
-    """twice test_gpu_dense._check's bound: |d| <= 2 (1e-5 |ref| + frac max|ref|)"""
-    got = got.detach().double().cpu().numpy()
-    ref = ref.detach().double().cpu().numpy()
-    scale = float(np.abs(ref).max(initial=0.0))
-    d = np.abs(got - ref)
-    parity_report.record(name, got, ref, 2 * RTOL, 2 * frac)
-    print(f"{name}: max|d| {d.max(initial=0.0):.3e}  max|ref| {scale:.3e}")
-    bad = d > 2 * (RTOL * np.abs(ref) + frac * scale)
-    assert not bad.any(), f"{name}: {int(bad.sum())}/{bad.size} beyond tol, max|d| {d.max():.3e}, max|ref| {scale:.3e}"
-
-
 @pytest.mark.parametrize("name", ["deep", "opaque"])
 def test_against_colour_path(device, mode, name):
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     gC, gD, gA = _weights(cam, device)
     _, _, inv, alpha, ex = _raw_aux(cam, leaves, deg, device)
     depth = ex["depth"]
@@ -257,7 +205,7 @@ def test_against_colour_path(device, mode, name):
     _hip(cam, leaves, deg, device, aux=False, gC=gAD, colors=zcols, into=r)
     got, ref = _grads(t), _grads(r)
     for k in LEAVES:
-        _check2(got[k], ref[k], f"d{k} vs colour path", 5e-5 if k in CHAIN else RTOL)
+        check_tol(got[k], ref[k], f"d{k} vs colour path", frac=5e-5 if k in CHAIN else RTOL, times=2)
 
 
 # ------------------------------------------------------------------------------------------
@@ -270,13 +218,10 @@ def _dense(name, cam, leaves, deg, device, dtype):
     """render_local_aux on copies of the leaves in dtype (graph kept: one forward, several losses)."""
     key = (name, dtype)
     if key not in _DENSE:
-        W, H = cam.image_width, cam.image_height
         t = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in leaves.items()}
         res = dense_ref_aux.render_local_aux(
-            t["means3D"], t["means2D"], t["opacities"], cam.world_view_transform.to(device, dtype),
-            cam.full_proj_transform.to(device, dtype), cam.camera_center.to(device, dtype), math.tan(cam.FoVx / 2),
-            math.tan(cam.FoVy / 2), W, H, torch.zeros(3, dtype=dtype, device=device), shs=t["shs"], deg=deg,
-            scales=t["scales"], rots=t["rotations"])
+            t["means3D"], t["means2D"], t["opacities"], *dense_cases.dense_args(cam, device, dtype),
+            torch.zeros(3, dtype=dtype, device=device), shs=t["shs"], deg=deg, scales=t["scales"], rots=t["rotations"])
         _DENSE[key] = (t, res)
     return _DENSE[key]
 
@@ -301,32 +246,6 @@ def _dense_grads(key, t, outs, ws):
     return _DENSE_GRADS[key]
 
 
-def _np(x, keep=None):
-    x = x.detach().double().cpu().numpy()
-    return x if keep is None else x[keep]
-
-
-def _check(got, ref, name, keep, frac=RTOL):
-    got, ref = _np(got, keep), _np(ref, keep)
-    scale = float(np.abs(ref).max(initial=0.0))
-    d = np.abs(got - ref)
-    parity_report.record(name, got, ref, RTOL, frac)
-    print(f"{name}: max|d| {d.max(initial=0.0):.3e}  max|ref| {scale:.3e}")
-    bad = d > RTOL * np.abs(ref) + frac * scale
-    assert not bad.any(), f"{name}: {int(bad.sum())}/{bad.size} beyond tol, max|d| {d.max():.3e}, max|ref| {scale:.3e}"
-
-
-def _check_4x(got, ref, f32, name, keep, enforce=True):
-    """the conditioning rule: max|hip - f64| <= 4 max|dense f32 - f64| + 1e-5 max|ref|
-    (enforce=False: the figures are printed only)"""
-    g, r, n = _np(got, keep), _np(ref, keep), _np(f32, keep)
-    d_gpu, d_32, scale = np.abs(g - r).max(initial=0.0), np.abs(n - r).max(initial=0.0), np.abs(r).max(initial=0.0)
-    bound = 4.0 * d_32 + RTOL * scale
-    print(f"  {name}: max|hip - f64| {d_gpu:.3e}  max|dense f32 - f64| {d_32:.3e}  max|ref| {scale:.3e}  "
-          f"({d_gpu / bound if bound > 0 else 0.0:.2f} of the bound)")
-    assert d_gpu <= bound or not enforce, (name, d_gpu, d_32, scale)
-
-
 SCENE_SEED = {"sparse": 41, "opaque": 49, "empty-tile": 41}
 LOSSES = {"aux": (False, True, True), "colour": (True, False, False), "all": (True, True, True)}
 
@@ -336,7 +255,7 @@ LOSSES = {"aux": (False, True, True), "colour": (True, False, False), "all": (Tr
 def test_against_dense_fp64(device, mode, name, loss):
     from diff_gaussian_rasterization import GaussianRasterizer
 
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     W, H, P = cam.image_width, cam.image_height, leaves["means3D"].shape[0]
     ref, (rimg, rradii, flag, rinv, ralpha) = _dense(name, cam, leaves, deg, device, torch.float64)
     r32, (img32, _, _, inv32, alpha32) = _dense(name, cam, leaves, deg, device, torch.float32)
@@ -350,16 +269,7 @@ def test_against_dense_fp64(device, mode, name, loss):
     rdiff = (radii.cpu() != rradii.cpu()).numpy()
     assert rdiff.mean() <= 1e-3, f"{int(rdiff.sum())} radii differ"
     fl = flag.cpu().numpy().copy()
-    with torch.no_grad():
-        f = torch.float64
-        q = dense_ref._prep(ref["means3D"], ref["means2D"], ref["opacities"], cam.world_view_transform.to(device, f),
-                            cam.full_proj_transform.to(device, f), cam.camera_center.to(device, f),
-                            math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), W, H, shs=ref["shs"], deg=deg,
-                            scales=ref["scales"], rots=ref["rotations"])
-    rect = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-    for i in np.nonzero(rdiff)[0]:
-        x0, y0, x1, y1 = rect[i]
-        fl[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+    dense_cases.wide_mask(dense_cases.rect_and_radii(cam, leaves, deg, device)[0], rdiff, W, H, into=fl)
     print(f"\n[dense aux {name}/{loss}] flagged pixels {int(fl.sum())}/{fl.size}, radii differing {int(rdiff.sum())}/{P}")
     assert fl.mean() <= 0.02
     keep_px = torch.from_numpy(~fl).to(device)
@@ -375,12 +285,12 @@ def test_against_dense_fp64(device, mode, name, loss):
     keep_g = ~rdiff
 
     tag = f"{name}/{loss}"
-    _check(img.permute(1, 2, 0), rimg.permute(1, 2, 0), f"image [{tag}]", ~fl)
-    _check_4x(inv[0], rinv[0], inv32[0], f"invdepth [{tag}]", ~fl)
-    _check_4x(alpha[0], ralpha[0], alpha32[0], f"alpha [{tag}]", ~fl)
+    check_tol(img.permute(1, 2, 0), rimg.permute(1, 2, 0), f"image [{tag}]", ~fl)
+    check_4x(inv[0], rinv[0], inv32[0], f"invdepth [{tag}]", ~fl)
+    check_4x(alpha[0], ralpha[0], alpha32[0], f"alpha [{tag}]", ~fl)
     for k in LEAVES:
-        _check_4x(got[k], g_ref[k], g_32[k], f"d{k} [{tag}]", keep_g, enforce=k in CHAIN)
-        _check(got[k], g_ref[k], f"d{k} [{tag}]", keep_g, frac=5e-5 if k in CHAIN else RTOL)
+        check_4x(got[k], g_ref[k], g_32[k], f"d{k} [{tag}]", keep_g, enforce=k in CHAIN)
+        check_tol(got[k], g_ref[k], f"d{k} [{tag}]", keep_g, frac=5e-5 if k in CHAIN else RTOL)
 
 
 # ------------------------------------------------------------------------------------------
@@ -389,14 +299,14 @@ def test_against_dense_fp64(device, mode, name, loss):
 def _tiny_call(device, t, **kw):
     from diff_gaussian_rasterization import GaussianRasterizer
 
-    cam, _, deg = _scene("empty-tile", device)
+    cam, _, deg = dense_cases.scene("empty-tile", device)
     s = gs_scenes.raster_settings_for(cam, deg, device=device)
     return GaussianRasterizer(s)(means3D=t["means3D"], means2D=t["means2D"], opacities=t["opacities"], shs=t["shs"],
                                  scales=t["scales"], rotations=t["rotations"], **kw)
 
 
 def _tiny_leaves(device):
-    _, leaves, _ = _scene("empty-tile", device)
+    _, leaves, _ = dense_cases.scene("empty-tile", device)
     return {k: v.detach().clone().requires_grad_(True) for k, v in leaves.items()}
 
 
@@ -438,7 +348,7 @@ def test_accumulating_sink(device, mode):
     max|grad|) (the depth term of this scene is smaller than the total)."""
     from diff_gaussian_rasterization import register_gradient_sink, unregister_gradient_sink
 
-    cam, _, _ = _scene("empty-tile", device)
+    cam, _, _ = dense_cases.scene("empty-tile", device)
     gC, gD, gA = _weights(cam, device)
     t0 = _tiny_leaves(device)
     out = _tiny_call(device, t0, aux_outputs=True)
@@ -480,7 +390,7 @@ def test_accumulating_sink(device, mode):
 def test_empty_scene_returns_zeros(device, mode):
     from diff_gaussian_rasterization import GaussianRasterizer
 
-    cam, leaves, deg = _scene("empty-tile", device)
+    cam, leaves, deg = dense_cases.scene("empty-tile", device)
     s = gs_scenes.raster_settings_for(cam, deg, device=device)
     e = {k: v[:0].contiguous() for k, v in leaves.items()}
     img, radii, inv, alpha = GaussianRasterizer(s)(
@@ -494,7 +404,7 @@ def test_empty_scene_returns_zeros(device, mode):
 def test_single_aux_gradients(device, mode):
     """dL/dalpha only and dL/dinvdepth only both run, and (linearity) add up to the run with both,
     within twice _check's bounds (two fp32 orders)."""
-    cam, leaves, deg = _scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     _, gD, gA = _weights(cam, device)
     _, ta = _hip(cam, leaves, deg, device, gA=gA)
     _, td = _hip(cam, leaves, deg, device, gD=gD)
@@ -503,4 +413,4 @@ def test_single_aux_gradients(device, mode):
     assert float(ga["opacities"].abs().max()) > 0 and float(gd["means3D"].abs().max()) > 0
     assert not ga["shs"].any() and not gd["shs"].any()
     for k in LEAVES:
-        _check2(ga[k] + gd[k], gb[k], f"d{k} alpha-only + invdepth-only", 5e-5 if k in CHAIN else RTOL)
+        check_tol(ga[k] + gd[k], gb[k], f"d{k} alpha-only + invdepth-only", frac=5e-5 if k in CHAIN else RTOL, times=2)

@@ -29,7 +29,8 @@ import torch
 import dense_ref
 import fused_views_cases as fvc
 import gs_scenes
-from test_gpu_dense import CHAIN, RTOL
+from gpu_checks import RTOL
+from test_gpu_dense import CHAIN
 
 pytestmark = pytest.mark.gpu
 

@@ -32,35 +32,21 @@ Scenes:
 import ctypes
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import dense_cases
 import dense_ref
 import dense_ref_aux
+import gpu_checks
 import gs_scenes
-import parity_report
+from gpu_checks import check_4x, check_tol, mode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
 EYE, TARGET = (0.7, -0.4, -1.1), (0.1, 0.2, 4.0)
 CAM_KERNELS = ("camera_grad", "camera_grad_finish")
 NAMES = ("viewmatrix", "projmatrix", "campos")
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture(params=[1, 0], ids=["exact", "fast"])
-def mode(request):
-    """Both numerics modes (the save / restore idiom of tests/test_gpu_aux.py)."""
-    prev = _lib().gs_set_exact_exp(request.param)
-    yield request.param
-    _lib().gs_set_exact_exp(prev)
 
 
 def _cam(W, H):
@@ -231,31 +217,12 @@ def _masked_weights(name, sc, device, radii):
                                 math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), W, H, shs=ref.get("shs"),
                                 deg=sc["deg"], colors=ref.get("colors"), scales=ref.get("scales"),
                                 rots=ref.get("rotations"), cov3D=ref.get("cov3D"))
-        rect = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-        for i in np.nonzero(rdiff)[0]:
-            x0, y0, x1, y1 = rect[i]
-            fl[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+        dense_cases.wide_mask(q["rect"].numpy(), rdiff, W, H, into=fl)
     print(f"\n[camera {name}] flagged pixels {int(fl.sum())}/{fl.size}, radii differing {int(rdiff.sum())}/{rdiff.size}, "
           f"visible {int((hr > 0).sum())}")
     assert fl.mean() <= 0.02
     keep_px = torch.from_numpy(~fl).to(device)
     return [w * keep_px[None] for w in _weights(sc, device)], fl, fl.tobytes()
-
-
-def _np(x):
-    return x.detach().double().cpu().numpy()
-
-
-def _check_4x(got, ref, f32, name):
-    """max|hip - f64| <= 4 max|dense f32 - f64| + 1e-5 max|f64|"""
-    g, r, n = _np(got), _np(ref), _np(f32)
-    d_gpu, d_32, scale = np.abs(g - r).max(initial=0.0), np.abs(n - r).max(initial=0.0), np.abs(r).max(initial=0.0)
-    bound = 4.0 * d_32 + RTOL * scale
-    if scale > 0:
-        parity_report.record(name, g, r, 0.0, bound / scale)
-    print(f"  {name}: max|hip - f64| {d_gpu:.3e}  max|dense f32 - f64| {d_32:.3e}  max|f64| {scale:.3e}  "
-          f"({d_gpu / bound if bound > 0 else 0.0:.2f} of the bound)")
-    assert d_gpu <= bound, (name, d_gpu, d_32, scale)
 
 
 def _cam_grads(cams):
@@ -279,17 +246,14 @@ def test_against_dense_fp64(device, mode, name):
     g64 = _dense_grads(name, sc, torch.float64, device, ws, mask)
     g32 = _dense_grads(name, sc, torch.float32, device, ws, mask)
     rimg = _dense(name, sc, torch.float64, device)[2][0]
-    keep = ~fl
-    d_img = np.abs(_np(outs[0].permute(1, 2, 0))[keep] - _np(rimg.permute(1, 2, 0))[keep])
-    r_img = np.abs(_np(rimg.permute(1, 2, 0))[keep])
-    assert (d_img <= RTOL * r_img + RTOL * r_img.max(initial=0.0)).all(), "image"
+    check_tol(outs[0].permute(1, 2, 0), rimg.permute(1, 2, 0), f"image [{name}]", ~fl)
     got = _cam_grads(cams)
     assert got[0].shape == (4, 4) and got[1].shape == (4, 4) and got[2].shape == (3,)
     # structural zeros, written as such
     assert torch.equal(got[0][:, 3], torch.zeros(4, device=device))
     assert torch.equal(got[1][:, 2], torch.zeros(4, device=device))
     for k, nm in enumerate(NAMES):
-        _check_4x(got[k], g64[k], g32[k], f"d{nm} [{name}]")
+        check_4x(got[k], g64[k], g32[k], f"d{nm} [{name}]")
     assert float(g64[0].abs().max()) > 0 and float(g64[1].abs().max()) > 0
     if name in ("D", "sh0"):  # precomputed colours, or a constant SH colour: the camera position enters nothing
         assert cams[2].grad is None or not cams[2].grad.any()
@@ -313,7 +277,7 @@ def test_empty_scene_gives_zero_gradients_and_no_launch(device, mode):
 
     sc = dict(_scene("small3", device))
     sc["leaves"] = {k: v[:0].contiguous() for k, v in sc["leaves"].items()}
-    lib = _lib()
+    lib = gpu_checks.lib()
     torch.cuda.synchronize()
     lib.gs_profile_collect()
     lib.gs_profile_reset()
@@ -357,7 +321,7 @@ def test_no_camera_tensor_requires_grad_launches_nothing(device, mode):
     sc = _scene("sh2", device)
     ws = _weights(sc, device)
     o0, r0, t0, _ = _hip(sc, device, ws, camera_grads=False, req=(False, False, False))
-    lib = _lib()
+    lib = gpu_checks.lib()
     lib.gs_profile_collect()
     lib.gs_profile_reset()
     lib.gs_profile_enable(1)
@@ -381,7 +345,7 @@ def test_only_viewmatrix_skips_the_sh_rows(device, mode):
     sc = _scene("sh2", device)
     ws = _weights(sc, device)
     _, _, _, full = _hip(sc, device, ws)
-    lib = _lib()
+    lib = gpu_checks.lib()
     assert lib.gs_debug_launch_log(1) in (0, 1)
     lib.gs_profile_collect()
     lib.gs_profile_reset()
@@ -487,7 +451,7 @@ def test_end_to_end_twist(device, mode):
         d, c = chain(dtype)
         torch.autograd.backward(list(c), [g[0], g[1], g[2]])
         want.append(d.grad)
-    _check_4x(delta.grad, want[0], want[1], "ddelta [twist, sh2]")
+    check_4x(delta.grad, want[0], want[1], "ddelta [twist, sh2]")
 
 
 # ------------------------------------------------------------------------------------------

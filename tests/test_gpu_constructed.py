@@ -22,17 +22,10 @@ import torch
 import constructed_scenes as cs_mod
 import gs_scenes
 from constructed_scenes import cached, oracle_forward
-from test_gpu_parity import (RTOL, _check_backward, _check_chain_noise, _check_forward_exact, _gpu_run, _lib,
-                             _oracle_scene)
+from gpu_checks import exact_mode  # noqa: F401
+from test_gpu_parity import RTOL, _check_backward, _check_chain_noise, _check_forward_exact, _gpu_run, _oracle_scene
 
-pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def exact_mode():
-    prev = _lib().gs_set_exact_exp(1)
-    yield
-    _lib().gs_set_exact_exp(prev)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("exact_mode")]
 
 
 _GRADS = (("means2D", "dmeans2D"), ("opacities", "dopacity"), ("means3D", "dmeans3D"), ("shs", "dsh"),

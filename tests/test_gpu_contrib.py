@@ -43,59 +43,13 @@ import numpy as np
 import pytest
 import torch
 
-import dense_ref
+import dense_cases
 import dense_ref_aa
 import dense_ref_contrib
 import gs_scenes
-import parity_report
+from gpu_checks import check_4x, check_tol, mode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-5
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture(params=[1, 0], ids=["exact", "fast"])
-def mode(request):
-    """Both numerics modes (the save / restore idiom of tests/test_gpu_parity.py)."""
-    prev = _lib().gs_set_exact_exp(request.param)
-    yield request.param
-    _lib().gs_set_exact_exp(prev)
-
-
-_SCENES = {}
-
-
-def _scene(name, device):
-    """(cam, leaves, sh degree) of a named scene; built once."""
-    if name not in _SCENES:
-        cam = gs_scenes.identity_camera(200, 120)
-        if name in ("sparse", "empty-tile", "sparse-low"):
-            sc, deg = gs_scenes.random_gaussians(2000, 3, cam=cam, seed=41), 3
-        elif name == "deep":
-            sc, deg = gs_scenes.random_gaussians(6000, 1, cam=cam, seed=47, scale_range=(0.01, 0.08)), 1
-        else:
-            sc, deg = gs_scenes.random_gaussians(8000, 1, cam=cam, seed=49, scale_range=(0.02, 0.12)), 1
-            sc.opacities = 0.5 + 0.49 * sc.opacities
-        if name == "sparse-low":
-            sc.opacities = sc.opacities.clone()
-            sc.opacities[_lowered()] = 0.003
-        leaves = {k: getattr(sc, k) for k in ("means3D", "opacities", "shs", "scales", "rotations")}
-        if name == "empty-tile":
-            leaves = {k: v[:3].contiguous() for k, v in leaves.items()}
-            cam = gs_scenes.identity_camera(72, 40)
-        _SCENES[name] = (cam, {k: v.to(device) for k, v in leaves.items()}, deg)
-    return _SCENES[name]
-
-
-def _lowered():
-    return torch.rand(2000, generator=torch.Generator().manual_seed(7)) < 1.0 / 3.0
-
 
 def _map(cam, device, seed=13):
     """a random positive weight map in [0.25, 1.25)"""
@@ -167,7 +121,7 @@ def _raw(cam, leaves, deg, device, dpix, stats):
 def test_bit_identities(device, mode, name):
     import gs_importance
 
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     m = _map(cam, device)
@@ -248,7 +202,7 @@ def test_bit_identities(device, mode, name):
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["sparse", "deep", "opaque", "empty-tile"])
 def test_wsum_telescopes_to_alpha(device, mode, name):
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     st = _stats(cam, leaves, deg, device)
     _, _, _, alpha = _render(cam, leaves, deg, device, aux=True)
@@ -266,23 +220,9 @@ def test_wsum_telescopes_to_alpha(device, mode, name):
 # ------------------------------------------------------------------------------------------
 # 3. against the existing path
 # ------------------------------------------------------------------------------------------
-def _check2(got, ref, name):
-    """twice test_gpu_dense._check's bound: |d| <= 2 (1e-5 |ref| + 1e-5 max|ref|)"""
-    got = got.detach().double().cpu().numpy()
-    ref = ref.detach().double().cpu().numpy()
-    scale = float(np.abs(ref).max(initial=0.0))
-    d = np.abs(got - ref)
-    tol = 2 * (RTOL * np.abs(ref) + RTOL * scale)
-    parity_report.record(name, got, ref, 2 * RTOL, 2 * RTOL)
-    print(f"{name}: max|d| {d.max(initial=0.0):.3e}  max|ref| {scale:.3e}  "
-          f"({float((d / np.maximum(tol, 1e-300)).max(initial=0.0)):.3f} of the bound)")
-    bad = d > tol
-    assert not bad.any(), f"{name}: {int(bad.sum())}/{bad.size} beyond tol, max|d| {d.max():.3e}, max|ref| {scale:.3e}"
-
-
 @pytest.mark.parametrize("name", ["sparse", "deep", "opaque"])
 def test_wsum_against_the_colour_gradient(device, mode, name):
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     m = _map(cam, device)
@@ -294,7 +234,7 @@ def test_wsum_against_the_colour_gradient(device, mode, name):
     torch.cuda.synchronize()
     assert torch.equal(radii, st.radii)
     print()
-    _check2(st.wsum, cols.grad[:, 0], f"[{name}] wsum vs dL/dcolors_precomp[:, 0]")
+    check_tol(st.wsum, cols.grad[:, 0], f"[{name}] wsum vs dL/dcolors_precomp[:, 0]", times=2)
 
 
 # ------------------------------------------------------------------------------------------
@@ -304,12 +244,10 @@ _DENSE = {}
 
 
 def _dense(name, cam, leaves, deg, device, dtype, weights, **flags):
-    W, H = cam.image_width, cam.image_height
     t = {k: v.detach().to(dtype) for k, v in leaves.items()}
     return dense_ref_contrib.contributions_local(
-        t["means3D"], torch.zeros_like(t["means3D"]), t["opacities"], cam.world_view_transform.to(device, dtype),
-        cam.full_proj_transform.to(device, dtype), cam.camera_center.to(device, dtype), math.tan(cam.FoVx / 2),
-        math.tan(cam.FoVy / 2), W, H, weights=weights, shs=t["shs"], deg=deg, scales=t["scales"],
+        t["means3D"], t["means2D"], t["opacities"], *dense_cases.dense_args(cam, device, dtype), weights=weights,
+        shs=t["shs"], deg=deg, scales=t["scales"],
         rots=t["rotations"], **flags)
 
 
@@ -319,21 +257,9 @@ def _dense_case(name, cam, leaves, deg, device, hip_radii):
     differing radii."""
     c = _DENSE.setdefault(name, {})
     if "rect" not in c:
-        W, H = cam.image_width, cam.image_height
-        f = torch.float64
-        q = dense_ref._prep(leaves["means3D"].to(f), torch.zeros_like(leaves["means3D"], dtype=f),
-                            leaves["opacities"].to(f), cam.world_view_transform.to(device, f),
-                            cam.full_proj_transform.to(device, f), cam.camera_center.to(device, f),
-                            math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), W, H, shs=leaves["shs"].to(f), deg=deg,
-                            scales=leaves["scales"].to(f), rots=leaves["rotations"].to(f))
-        c["rect"] = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-        c["radii"] = q["radii"].cpu()
+        c["rect"], c["radii"] = dense_cases.rect_and_radii(cam, leaves, deg, device)
     rdiff = (hip_radii.cpu() != c["radii"]).numpy()
-    # a Gaussian whose radius differs composites into a rectangle up to one tile wider in fp32
-    wide = np.zeros((cam.image_height, cam.image_width), bool)
-    for i in np.nonzero(rdiff)[0]:
-        x0, y0, x1, y1 = c["rect"][i]
-        wide[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+    wide = dense_cases.wide_mask(c["rect"], rdiff, cam.image_width, cam.image_height)
     if "wide" not in c or not np.array_equal(c["wide"], wide):
         c["wide"] = wide
         c["f64"] = _dense(name, cam, leaves, deg, device, torch.float64, _map(cam, device, seed=17).double(),
@@ -345,21 +271,9 @@ def _dense_case(name, cam, leaves, deg, device, hip_radii):
     return c["m"], fl, rdiff, c["f64"], c["f32"]
 
 
-def _check_4x(got, ref, f32, name, keep):
-    """the conditioning rule: max|hip - f64| <= 4 max|dense f32 - f64| + 1e-5 max|ref|"""
-    g, r, n = (x.detach().double().cpu().numpy()[keep] for x in (got, ref, f32))
-    d_gpu, d_32, scale = np.abs(g - r).max(initial=0.0), np.abs(n - r).max(initial=0.0), np.abs(r).max(initial=0.0)
-    bound = 4.0 * d_32 + RTOL * scale
-    parity_report.record(name, g, r, 0.0, bound / scale if scale > 0 else 0.0)
-    plain = float((np.abs(n - r) / (RTOL * np.abs(r) + RTOL * scale)).max(initial=0.0)) if scale > 0 else 0.0
-    print(f"  {name}: max|hip - f64| {d_gpu:.3e}  max|dense f32 - f64| {d_32:.3e}  max|ref| {scale:.3e}  "
-          f"({d_gpu / bound if bound > 0 else 0.0:.2f} of the bound; dense f32 at {plain:.2f} of 1e-5|ref| + 1e-5 max)")
-    assert d_gpu <= bound, (name, d_gpu, d_32, scale)
-
-
 @pytest.mark.parametrize("name", ["sparse", "deep", "opaque"])
 def test_against_dense_fp64(device, mode, name):
-    cam, leaves, deg = _scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     P = leaves["means3D"].shape[0]
     radii = _stats(cam, leaves, deg, device).radii
     m, fl, rdiff, r64, r32 = _dense_case(name, cam, leaves, deg, device, radii)
@@ -375,16 +289,16 @@ def test_against_dense_fp64(device, mode, name):
           f"{int((c32 != ref_cnt).sum())}), max {int(ref_cnt.max())}")
     assert int(ref_cnt.max()) > 10
     assert np.array_equal(cnt, ref_cnt)
-    _check_4x(st.wsum, r64["wsum"], r32["wsum"], f"[{name}] wsum", keep)
-    _check_4x(st.wmax, r64["wmax"], r32["wmax"], f"[{name}] wmax", keep)
+    check_4x(st.wsum, r64["wsum"], r32["wsum"], f"[{name}] wsum", keep)
+    check_4x(st.wmax, r64["wmax"], r32["wmax"], f"[{name}] wmax", keep)
 
 
 # ------------------------------------------------------------------------------------------
 # 5. pruning keeps the image
 # ------------------------------------------------------------------------------------------
 def test_pruning_keeps_the_image(device, mode):
-    cam, leaves, deg = _scene("sparse-low", device)
-    low = _lowered().to(device)
+    cam, leaves, deg = dense_cases.scene("sparse-low", device)
+    low = dense_cases.lowered().to(device)
     assert 600 < int(low.sum()) < 740
     img, radii, _, alpha = _render(cam, leaves, deg, device, aux=True)
     # a pixel can only have stopped if its T fell below 0.01: removing a never-composited Gaussian is
@@ -403,7 +317,7 @@ def test_prune_on_a_model_with_fused_adam(device, mode):
     import gs_importance
     import gs_train
 
-    cam, leaves, deg = _scene("sparse-low", device)
+    cam, leaves, deg = dense_cases.scene("sparse-low", device)
     P = leaves["means3D"].shape[0]
 
     class Model:
@@ -440,7 +354,7 @@ def test_prune_on_a_model_with_fused_adam(device, mode):
     assert float(alpha.max()) <= 0.98
     st = _stats(cam, full, deg, device)
     keep = gs_importance.keep_mask(st, min_count=1)
-    assert torch.equal(~keep, _lowered().to(device))
+    assert torch.equal(~keep, dense_cases.lowered().to(device))
     old = {a: getattr(mdl, a) for a in raw}
     want = {a: old[a].detach()[keep].clone() for a in raw}
     mom = {a: {k: (v if k == "step" else v[keep].clone()) for k, v in mdl.optimizer.state[old[a]].items()}
@@ -471,7 +385,7 @@ def test_prune_on_a_model_with_fused_adam(device, mode):
 # 6. interface
 # ------------------------------------------------------------------------------------------
 def test_antialiasing_equals_the_plain_call_with_the_compensated_opacities(device, mode):
-    cam, leaves, deg = _scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     H, W = cam.image_height, cam.image_width
     m = _map(cam, device)
     s = dense_ref_aa.aa_scale(leaves["means3D"], cam.world_view_transform.to(device), math.tan(cam.FoVx / 2),
@@ -483,15 +397,15 @@ def test_antialiasing_equals_the_plain_call_with_the_compensated_opacities(devic
     off = _stats(cam, leaves, deg, device, pixel_weights=m)
     assert torch.equal(aa.radii, plain.radii) and not torch.equal(aa.wsum, off.wsum)
     print()
-    _check2(aa.wsum, plain.wsum, "antialiased wsum vs compensated opacities")
-    _check2(aa.wmax, plain.wmax, "antialiased wmax vs compensated opacities")
-    _check2(aa.count, plain.count, "antialiased count vs compensated opacities")
+    check_tol(aa.wsum, plain.wsum, "antialiased wsum vs compensated opacities", times=2)
+    check_tol(aa.wmax, plain.wmax, "antialiased wmax vs compensated opacities", times=2)
+    check_tol(aa.count, plain.count, "antialiased count vs compensated opacities", times=2)
 
 
 def test_refused_inputs(device):
     import gs_importance
 
-    cam, leaves, deg = _scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     H, W = cam.image_height, cam.image_width
     r = _rasterizer(cam, deg, device)
     kw = _inputs(leaves)

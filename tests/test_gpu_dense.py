@@ -18,40 +18,24 @@ repeated division, so fp32 itself moves them by about 1e-5 of their max: they ge
 scale_modifier case, where the dense fp32 run deviates as much) and, as the conditioning check, a
 max deviation within 4x that of the same dense reference evaluated in fp32 (one other valid fp32
 order), plus 1e-5 of the max."""
-import math
-
-import numpy as np
 import pytest
 import torch
 
+import dense_cases
 import dense_ref
 import gs_scenes
-import parity_report
+from gpu_checks import check_4x, check_tol
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-5
 CHAIN = ("means2D", "means3D", "scales", "rotations", "cov3D")
-
-
-def _check(got, ref, name, keep, frac=RTOL):
-    got = got.detach().double().cpu().numpy()[keep]
-    ref = ref.detach().double().cpu().numpy()[keep]
-    scale = float(np.abs(ref).max(initial=0.0))
-    d = np.abs(got - ref)
-    parity_report.record(name, got, ref, RTOL, frac)
-    bad = d > RTOL * np.abs(ref) + frac * scale
-    print(f"{name}: max|d| {d.max(initial=0.0):.3e}  max|ref| {scale:.3e}")
-    assert not bad.any(), f"{name}: {int(bad.sum())}/{bad.size} beyond tol, max|d| {d.max():.3e}, max|ref| {scale:.3e}"
 
 
 def _dense(cam, leaves, W, H, bg, deg, mod, dtype, device, flag_rel=1e-5, flag_T_rel=None):
     """dense_ref.render_local on copies of `leaves` in `dtype` (their grads by autograd)."""
     t = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in leaves.items()}
     res = dense_ref.render_local(
-        t["means3D"], t["means2D"], t["opacities"], cam.world_view_transform.to(device, dtype),
-        cam.full_proj_transform.to(device, dtype), cam.camera_center.to(device, dtype), math.tan(cam.FoVx / 2),
-        math.tan(cam.FoVy / 2), W, H, bg.to(dtype), shs=t.get("shs"), deg=deg, colors=t.get("colors"),
+        t["means3D"], t["means2D"], t["opacities"], *dense_cases.dense_args(cam, device, dtype), bg.to(dtype), shs=t.get("shs"), deg=deg, colors=t.get("colors"),
         scales=t.get("scales"), rots=t.get("rotations"), cov3D=t.get("cov3D"), mod=mod, flag_rel=flag_rel,
         flag_T_rel=flag_T_rel)
     return t, res
@@ -80,17 +64,11 @@ def _run_and_compare(cam, leaves, W, H, bg, deg=0, mod=1.0, seed=0, device=None,
     assert rdiff.mean() <= 1e-3, f"{int(rdiff.sum())} radii differ"
     fl = flag.cpu().numpy()
     with torch.no_grad():
-        f = torch.float64
-        q = dense_ref._prep(ref["means3D"], ref["means2D"], ref["opacities"], cam.world_view_transform.to(device, f),
-                            cam.full_proj_transform.to(device, f), cam.camera_center.to(device, f),
-                            math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), W, H, shs=ref.get("shs"), deg=deg,
+        q = dense_ref._prep(ref["means3D"], ref["means2D"], ref["opacities"],
+                            *dense_cases.dense_args(cam, device, torch.float64), shs=ref.get("shs"), deg=deg,
                             colors=ref.get("colors"), scales=ref.get("scales"), rots=ref.get("rotations"),
                             cov3D=ref.get("cov3D"), mod=mod)
-    rect = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-    # a Gaussian whose radius differs composites into a rectangle up to one tile wider in fp32
-    for i in np.nonzero(rdiff)[0]:
-        x0, y0, x1, y1 = rect[i]
-        fl[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+    dense_cases.wide_mask(q["rect"].numpy(), rdiff, W, H, into=fl)
     print(f"\n[dense] flagged pixels {int(fl.sum())}/{fl.size}, radii differing {int(rdiff.sum())}/{P}")
     assert fl.mean() <= 0.02
     # the backward runs with dL/dpix zeroed at the flagged pixels: a pixel with dL/dpix = 0 adds
@@ -103,19 +81,13 @@ def _run_and_compare(cam, leaves, W, H, bg, deg=0, mod=1.0, seed=0, device=None,
     torch.cuda.synchronize()
     keep_g = ~rdiff
 
-    _check(img.permute(1, 2, 0), rimg.permute(1, 2, 0), "image", ~fl)
+    check_tol(img.permute(1, 2, 0), rimg.permute(1, 2, 0), "image", ~fl)
     for k in hip:
         if k not in CHAIN:
-            _check(hip[k].grad, ref[k].grad, f"d{k}", keep_g)
+            check_tol(hip[k].grad, ref[k].grad, f"d{k}", keep_g)
             continue
-        _check(hip[k].grad, ref[k].grad, f"d{k}", keep_g, frac=chain_frac)
-        g = hip[k].grad.detach().double().cpu().numpy()[keep_g]
-        r = ref[k].grad.detach().double().cpu().numpy()[keep_g]
-        n = r32[k].grad.detach().double().cpu().numpy()[keep_g]
-        d_gpu, d_32, scale = np.abs(g - r).max(initial=0.0), np.abs(n - r).max(initial=0.0), np.abs(r).max(initial=0.0)
-        print(f"  d{k}: max|hip - f64| {d_gpu:.3e}  max|dense f32 - f64| {d_32:.3e}  ({d_gpu / scale:.2e} of max)")
-        if noise_check:
-            assert d_gpu <= 4.0 * d_32 + RTOL * scale, (k, d_gpu, d_32, scale)
+        check_tol(hip[k].grad, ref[k].grad, f"d{k}", keep_g, frac=chain_frac)
+        check_4x(hip[k].grad, ref[k].grad, r32[k].grad, f"d{k}", keep_g, enforce=noise_check)
 
 
 CASES = [(2000, 3, 192, 128, 0.0, 41, None), (6000, 2, 320, 200, 0.3, 42, None),

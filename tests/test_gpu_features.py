@@ -33,20 +33,13 @@ import numpy as np
 import pytest
 import torch
 
-import dense_ref
+import dense_cases
 import dense_ref_features
 import gs_scenes
 import test_gpu_contrib as tc
+from gpu_checks import check_4x, check_tol, mode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(params=[1, 0], ids=["exact", "fast"])
-def mode(request):
-    """Both numerics modes (the save / restore idiom of tests/test_gpu_parity.py)."""
-    prev = tc._lib().gs_set_exact_exp(request.param)
-    yield request.param
-    tc._lib().gs_set_exact_exp(prev)
 
 
 def _G():
@@ -93,7 +86,7 @@ def _randn(shape, seed, device):
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["sparse", "opaque", "empty-tile"])
 def test_run_to_run_and_group_independence(device, mode, name):
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     view = _view(cam, leaves, deg, device)
@@ -124,7 +117,7 @@ def test_run_to_run_and_group_independence(device, mode, name):
 def test_colour_and_inverse_depth_identities(device, mode, name):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     G = _G()
@@ -155,7 +148,7 @@ def test_colour_and_inverse_depth_identities(device, mode, name):
 def test_backward_is_wsum_per_channel_and_accumulates(device, mode, name):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     G = _G()
     C = G + 1
@@ -182,7 +175,7 @@ def test_backward_is_wsum_per_channel_and_accumulates(device, mode, name):
 def test_features_leave_the_colour_backward_alone(device, mode, name):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     C = 2 * _G() + 3
@@ -223,7 +216,7 @@ def test_features_leave_the_colour_backward_alone(device, mode, name):
 def test_no_gaussians_give_zeros(device, mode):
     import gs_features
 
-    cam, leaves, deg = tc._scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     H, W = cam.image_height, cam.image_width
     none = {k: v[:0].contiguous() for k, v in leaves.items()}
     view = _view(cam, none, deg, device)
@@ -239,7 +232,7 @@ def test_no_gaussians_give_zeros(device, mode):
 def test_empty_tiles_are_written_as_zeros(device, mode):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = tc._scene("empty-tile", device)
+    cam, leaves, deg = dense_cases.scene("empty-tile", device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     view = _view(cam, leaves, deg, device)
@@ -264,7 +257,7 @@ def test_empty_tiles_are_written_as_zeros(device, mode):
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["sparse", "deep", "opaque"])
 def test_backward_against_the_colour_gradient(device, mode, name):
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     g = gs_scenes.dl_dimage(H, W, seed=5, scale=1.0).to(device)
@@ -277,7 +270,7 @@ def test_backward_against_the_colour_gradient(device, mode, name):
     assert torch.equal(radii, view.radii)
     d = _bwd(view, g)
     print()
-    tc._check2(d, cols.grad, f"[{name}] dL/dfeatures vs dL/dcolors_precomp")
+    check_tol(d, cols.grad, f"[{name}] dL/dfeatures vs dL/dcolors_precomp", times=2)
 
 
 # ------------------------------------------------------------------------------------------
@@ -287,7 +280,7 @@ def test_backward_against_the_colour_gradient(device, mode, name):
 def test_channel_of_ones_against_the_aux_alpha(device, mode, name):
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     view = _view(cam, leaves, deg, device)
@@ -310,12 +303,10 @@ _DENSE = {}
 
 
 def _dense(cam, leaves, deg, device, dtype, features, g, **flags):
-    W, H = cam.image_width, cam.image_height
     t = {k: v.detach().to(dtype) for k, v in leaves.items()}
     return dense_ref_features.features_local(
-        t["means3D"], torch.zeros_like(t["means3D"]), t["opacities"], cam.world_view_transform.to(device, dtype),
-        cam.full_proj_transform.to(device, dtype), cam.camera_center.to(device, dtype), math.tan(cam.FoVx / 2),
-        math.tan(cam.FoVy / 2), W, H, features.to(dtype), g=g.to(dtype), shs=t["shs"], deg=deg, scales=t["scales"],
+        t["means3D"], t["means2D"], t["opacities"], *dense_cases.dense_args(cam, device, dtype), features.to(dtype),
+        g=g.to(dtype), shs=t["shs"], deg=deg, scales=t["scales"],
         rots=t["rotations"], **flags)
 
 
@@ -326,23 +317,11 @@ def _dense_case(name, cam, leaves, deg, device, hip_radii, C):
     c = _DENSE.setdefault(name, {})
     P = leaves["means3D"].shape[0]
     if "rect" not in c:
-        W, H = cam.image_width, cam.image_height
-        f = torch.float64
-        q = dense_ref._prep(leaves["means3D"].to(f), torch.zeros_like(leaves["means3D"], dtype=f),
-                            leaves["opacities"].to(f), cam.world_view_transform.to(device, f),
-                            cam.full_proj_transform.to(device, f), cam.camera_center.to(device, f),
-                            math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), W, H, shs=leaves["shs"].to(f), deg=deg,
-                            scales=leaves["scales"].to(f), rots=leaves["rotations"].to(f))
-        c["rect"] = torch.stack([q["x0"], q["y0"], q["x1"], q["y1"]], 1).to(torch.int64).cpu().numpy()
-        c["radii"] = q["radii"].cpu()
+        c["rect"], c["radii"] = dense_cases.rect_and_radii(cam, leaves, deg, device)
         c["F"] = _randn((P, C), 201, device)
         c["g0"] = _randn((C, cam.image_height, cam.image_width), 202, device)
     rdiff = (hip_radii.cpu() != c["radii"]).numpy()
-    # a Gaussian whose radius differs composites into a rectangle up to one tile wider in fp32
-    wide = np.zeros((cam.image_height, cam.image_width), bool)
-    for i in np.nonzero(rdiff)[0]:
-        x0, y0, x1, y1 = c["rect"][i]
-        wide[max(16 * y0 - 16, 0):16 * y1 + 16, max(16 * x0 - 16, 0):16 * x1 + 16] = True
+    wide = dense_cases.wide_mask(c["rect"], rdiff, cam.image_width, cam.image_height)
     if "wide" not in c or not np.array_equal(c["wide"], wide):
         c["wide"] = wide
         c["f64"] = _dense(cam, leaves, deg, device, torch.float64, c["F"], c["g0"], flag_rel=1e-3, flag_T_rel=1e-2,
@@ -356,7 +335,7 @@ def _dense_case(name, cam, leaves, deg, device, hip_radii, C):
 
 @pytest.mark.parametrize("name", ["sparse", "deep", "opaque"])
 def test_against_dense_fp64(device, mode, name):
-    cam, leaves, deg = tc._scene(name, device)
+    cam, leaves, deg = dense_cases.scene(name, device)
     P = leaves["means3D"].shape[0]
     C = _G() + 1
     view = _view(cam, leaves, deg, device)
@@ -367,8 +346,8 @@ def test_against_dense_fp64(device, mode, name):
     assert rdiff.mean() <= 1e-3, f"{int(rdiff.sum())} radii differ"
     out, d = _fwd(view, F), _bwd(view, g)
     keep_px = np.broadcast_to(~left_out, (C,) + left_out.shape)
-    tc._check_4x(out, r64["out"], r32["out"], f"[{name}] out", keep_px)
-    tc._check_4x(d, r64["dfeat"], r32["dfeat"], f"[{name}] dL/dfeatures", ~rdiff)
+    check_4x(out, r64["out"], r32["out"], f"[{name}] out", keep_px)
+    check_4x(d, r64["dfeat"], r32["dfeat"], f"[{name}] dL/dfeatures", ~rdiff)
 
 
 # ------------------------------------------------------------------------------------------
@@ -377,7 +356,7 @@ def test_against_dense_fp64(device, mode, name):
 def test_autograd_matches_the_raw_call(device, mode):
     import gs_features
 
-    cam, leaves, deg = tc._scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     G = _G()
@@ -407,7 +386,7 @@ def test_refused_inputs(device):
     import gs_features
     from diff_gaussian_rasterization import _C
 
-    cam, leaves, deg = tc._scene("sparse", device)
+    cam, leaves, deg = dense_cases.scene("sparse", device)
     H, W = cam.image_height, cam.image_width
     P = leaves["means3D"].shape[0]
     view = _view(cam, leaves, deg, device)

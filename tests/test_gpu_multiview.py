@@ -22,25 +22,14 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_checks
 import gs_scenes
-from test_gpu_parity import RTOL, _check_backward, _check_forward_exact, _gpu_run, _oracle_scene, _tol_check
+from gpu_checks import check_tol, exact_mode  # noqa: F401
+from test_gpu_parity import RTOL, _check_backward, _check_forward_exact, _gpu_run, _oracle_scene
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture
-def exact_mode():
-    prev = _lib().gs_set_exact_exp(1)
-    yield
-    _lib().gs_set_exact_exp(prev)
 
 
 def _free_port():
@@ -256,7 +245,7 @@ def test_raw_backward_returns_every_upstream_gradient(oracle, device, exact_mode
                           "drotations")):
         ref = gr[k].reshape(t.shape)
         assert np.abs(ref).max() > 0, k
-        _tol_check(t.cpu().numpy(), ref, k)
+        check_tol(t.cpu().numpy(), ref, k)
 
 
 def _occluded_scene():
@@ -345,7 +334,7 @@ def test_lookback_timeout_is_reported(device):
     out at once."""
     from diff_gaussian_rasterization import GaussianRasterizer
 
-    lib = _lib()
+    lib = gpu_checks.lib()
     cam = gs_scenes.identity_camera(320, 240)
     d = gs_scenes.random_gaussians(200_000, 0, cam=cam, seed=60).to(device)
     rast = GaussianRasterizer(gs_scenes.raster_settings_for(cam, 0, device=device))
@@ -434,7 +423,7 @@ def test_c4_ring_views_full_size(oracle, device):
             assert torch.isfinite(t.grad).all()
         assert float(p[1].grad.abs().max()) > 0
         del geom, binb, imgb, p, m2, img
-    prev = _lib().gs_set_exact_exp(1)
+    prev = gpu_checks.lib().gs_set_exact_exp(1)
     try:
         cam = cams[3]
         bg = np.zeros(3, np.float32)
@@ -446,7 +435,7 @@ def test_c4_ring_views_full_size(oracle, device):
         _, _, leaves = _gpu_run(cam, sc, device, bg, dp)
         _check_backward(oracle.backward(osc, dp), leaves)
     finally:
-        _lib().gs_set_exact_exp(prev)
+        gpu_checks.lib().gs_set_exact_exp(prev)
 
 
 def test_prepared_views_equal_single_view_calls(device):

@@ -15,7 +15,8 @@ import torch
 import constructed_scenes as cs_mod
 import gs_scenes
 from constructed_scenes import cached, oracle_forward
-from test_gpu_parity import _lib, _oracle_scene
+from gpu_checks import lib as _lib
+from test_gpu_parity import _oracle_scene
 
 pytestmark = pytest.mark.gpu
 

@@ -25,48 +25,10 @@ import pytest
 import torch
 
 import gs_scenes
-import parity_report
+from gpu_checks import RTOL, check_tol, exact_mode, fast_mode  # noqa: F401
 
-pytestmark = pytest.mark.gpu
-
-RTOL = 1e-5
-
-
-def _lib():
-    from diff_gaussian_rasterization import _native
-
-    return _native.load()
-
-
-@pytest.fixture(autouse=True)
-def exact_mode():
-    """Tests here run in the bit-exact numerics mode unless they switch to fast (and restore)."""
-    prev = _lib().gs_set_exact_exp(1)
-    yield
-    _lib().gs_set_exact_exp(prev)
-
-
-@pytest.fixture
-def fast_mode(exact_mode):
-    _lib().gs_set_exact_exp(0)
-    yield
-
-
-def _tol_check(gpu, ref, name, rtol=RTOL, frac=RTOL):
-    gpu = np.asarray(gpu, np.float64)
-    ref = np.asarray(ref, np.float64)
-    assert gpu.shape == ref.shape, (name, gpu.shape, ref.shape)
-    scale = max(np.abs(ref).max(), 1e-30)
-    tol = rtol * np.abs(ref) + frac * scale
-    parity_report.record(name, gpu, ref, rtol, frac)
-    bad = np.abs(gpu - ref) > tol
-    if bad.any():
-        idx = np.argwhere(bad)[:5]
-        detail = "; ".join(f"{tuple(int(x) for x in i)}: gpu {gpu[tuple(i)]:.6e} ref {ref[tuple(i)]:.6e} "
-                           f"tol {tol[tuple(i)]:.2e}" for i in idx)
-        raise AssertionError(f"{name}: {int(bad.sum())}/{bad.size} beyond tol; max|d|={np.abs(gpu - ref).max():.3e} "
-                             f"max|ref|={scale:.3e}; first: {detail}")
-
+# every test here runs in the bit-exact numerics mode unless it switches to fast (and restores)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("exact_mode")]
 
 def _oracle_scene(oracle, cam, sc, bg, colors=None, cov3D=None, deg=None, mod=1.0):
     deg = sc.sh_degree if deg is None else deg
@@ -142,18 +104,18 @@ def _check_backward(gr, leaves, colors=None, cov3D=None, rtol=RTOL, chain_frac=N
     covariance chain (dmeans3D, dscales, drotations, dcov3D); default rtol."""
     g = lambda k: leaves[k].grad.detach().cpu().numpy()  # noqa: E731
     cf = rtol if chain_frac is None else chain_frac
-    _tol_check(g("means2D"), gr["dmeans2D"], "dmeans2D", rtol, rtol)
-    _tol_check(g("opacities"), gr["dopacity"], "dopacity", rtol, rtol)
-    _tol_check(g("means3D"), gr["dmeans3D"], "dmeans3D", rtol, cf)
+    check_tol(g("means2D"), gr["dmeans2D"], "dmeans2D", rtol=rtol, frac=rtol)
+    check_tol(g("opacities"), gr["dopacity"], "dopacity", rtol=rtol, frac=rtol)
+    check_tol(g("means3D"), gr["dmeans3D"], "dmeans3D", rtol=rtol, frac=cf)
     if colors is None:
-        _tol_check(g("shs"), gr["dsh"], "dsh", rtol, rtol)
+        check_tol(g("shs"), gr["dsh"], "dsh", rtol=rtol, frac=rtol)
     else:
-        _tol_check(g("colors"), gr["dcolors"], "dcolors", rtol, rtol)
+        check_tol(g("colors"), gr["dcolors"], "dcolors", rtol=rtol, frac=rtol)
     if cov3D is None:
-        _tol_check(g("scales"), gr["dscales"], "dscales", rtol, cf)
-        _tol_check(g("rotations"), gr["drotations"], "drotations", rtol, cf)
+        check_tol(g("scales"), gr["dscales"], "dscales", rtol=rtol, frac=cf)
+        check_tol(g("rotations"), gr["drotations"], "drotations", rtol=rtol, frac=cf)
     else:
-        _tol_check(g("cov3D"), gr["dcov3D"], "dcov3D", rtol, cf)
+        check_tol(g("cov3D"), gr["dcov3D"], "dcov3D", rtol=rtol, frac=cf)
 
 
 CHAIN_KEYS = (("means3D", "dmeans3D"), ("scales", "dscales"), ("rotations", "drotations"), ("cov3D", "dcov3D"))
@@ -241,9 +203,9 @@ def _check_forward_fast(ofw, cam, sc, device, bg):
     assert near.sum() <= max(1, near.size // 1000), f"{int(near.sum())} near-threshold pixels"
     keep = ~near
     np.testing.assert_array_equal(ex["n_contrib"].cpu().numpy().astype(np.uint32)[keep], ofw["n_contrib"][keep])
-    _tol_check(ex["final_T"].cpu().numpy()[keep], ofw["final_T"][keep], "final_T")
+    check_tol(ex["final_T"].cpu().numpy()[keep], ofw["final_T"][keep], "final_T")
     col = color.cpu().numpy()
-    _tol_check(col[:, keep], ofw["color"][:, keep], "color")
+    check_tol(col[:, keep], ofw["color"][:, keep], "color")
     if near.any():  # decision-flip bound at the flagged pixels
         cmax = float(np.abs(ofw["rgb"][vis]).max(initial=0.0)) + float(np.abs(bg).max())
         dT = np.abs(ex["final_T"].cpu().numpy()[near] - ofw["final_T"][near])
@@ -268,7 +230,7 @@ def _check_backward_masked(gr, leaves, excl, rtol=RTOL):
     keep = ~excl
     g = lambda k: leaves[k].grad.detach().cpu().numpy()[keep]  # noqa: E731
     for k, o in _GRADS:
-        _tol_check(g(k), gr[o][keep], o, rtol, rtol)
+        check_tol(g(k), gr[o][keep], o, rtol=rtol, frac=rtol)
 
 
 def _fast_mode_parity(oracle, device, cam, sc, bg, dpix_seed=1):
@@ -292,7 +254,7 @@ def _fast_mode_parity(oracle, device, cam, sc, bg, dpix_seed=1):
     gm = oracle.backward(osc, dpix_m)
     gpu_m = {o: lm[k].grad.detach().cpu().numpy() for k, o in _GRADS}
     for k, o in _GRADS:
-        _tol_check(gpu_m[o], gm[o], o + " (all Gaussians, unflagged pixels)")
+        check_tol(gpu_m[o], gm[o], o + " (all Gaussians, unflagged pixels)")
     del lm
     _, _, lf = _gpu_run(cam, sc, device, bg, dpix)
     gf = oracle.backward(osc, dpix)
@@ -407,11 +369,11 @@ def test_needle_splats_conditioning(oracle, device):
     img, _, leaves = _gpu_run(cam, sc, device, bg, dpix)
     gr = oracle.backward(osc, dpix)
     g = lambda k: leaves[k].grad.detach().cpu().numpy()  # noqa: E731
-    _tol_check(g("means2D"), gr["dmeans2D"], "dmeans2D")
-    _tol_check(g("opacities"), gr["dopacity"], "dopacity")
-    _tol_check(g("shs"), gr["dsh"], "dsh")
+    check_tol(g("means2D"), gr["dmeans2D"], "dmeans2D")
+    check_tol(g("opacities"), gr["dopacity"], "dopacity")
+    check_tol(g("shs"), gr["dsh"], "dsh")
     for k, rk in (("means3D", "dmeans3D"), ("scales", "dscales"), ("rotations", "drotations")):
-        _tol_check(g(k), gr[rk], rk, rtol=1e-5, frac=5e-5)
+        check_tol(g(k), gr[rk], rk, rtol=1e-5, frac=5e-5)
     # the 5e-5 above is the conditioning, not the device: an fp32 order of the oracle's own sums
     # moves these gradients as far (and the device stays within NOISE_FACTOR of that)
     noise = _check_chain_noise(leaves, gr, oracle.backward_f32_acc(osc, dpix))

@@ -28,12 +28,11 @@ exactly 0 and 10 % exactly 1, g = dL/dimage standard normal.  Shapes (image W x 
 import ctypes
 import os
 
-import numpy as np
 import pytest
 import torch
 
 import gs_scenes
-import parity_report
+from gpu_checks import check_4x
 import sky_ref
 
 pytestmark = pytest.mark.gpu
@@ -90,19 +89,6 @@ def _hip(s, color, alpha, tex, g, color_grad=True, alpha_grad=True, tex_grad=Tru
     return img.detach(), None if c is None else c.grad, None if a is None else a.grad, t.grad
 
 
-def _check(name, hip, f64, f32):
-    """the 4x conditioning rule; prints and records measured error over bound"""
-    hip, f64, f32 = (np.asarray(t.detach().cpu(), np.float64) for t in (hip, f64, f32))
-    scale = np.abs(f64).max()
-    bound = 4.0 * np.abs(f32 - f64).max() + 1e-5 * scale
-    err = np.abs(hip - f64).max()
-    print(f"{name}: max|hip - f64| {err:.3e}  max|f32 - f64| {np.abs(f32 - f64).max():.3e}  bound {bound:.3e}  "
-          f"used {err / bound:.3f}  max|f64| {scale:.3e}")
-    parity_report.record(name, hip, f64, 0.0, bound / scale)
-    assert np.isfinite(hip).all()
-    assert err <= bound, f"{name}: {err:.3e} > {bound:.3e}"
-
-
 def _bits(t):
     return t.detach().contiguous().view(torch.int32)
 
@@ -135,7 +121,7 @@ def test_matches_fp64_reference(name, device):
     ref = _refs(name, device)
     img, dcolor, dalpha, dtex = _hip(s, color, alpha, tex, g)
     for tensor, got, k in (("image", img, 0), ("dL_dalpha", dalpha, 1), ("dL_dtexture", dtex, 2)):
-        _check(f"sky {name} {tensor}", got, ref[torch.float64][k], ref[torch.float32][k])
+        check_4x(got, ref[torch.float64][k], ref[torch.float32][k], f"sky {name} {tensor}")
     assert torch.equal(dcolor, g)
     # alpha as the rasterizer returns it, [1, H, W]: same bits, gradient in that shape
     img1, _, dalpha1, dtex1 = _hip(s, color, alpha[None], tex, g)
@@ -294,9 +280,9 @@ def test_render_with_sky_end_to_end(device):
     torch.cuda.synchronize()
     args = (rec.color, rec.alpha, sky.texture, g, s.viewmatrix, s.tanfovx, s.tanfovy)
     f64, f32 = sky_ref.reference(*args, torch.float64), sky_ref.reference(*args, torch.float32)
-    _check("sky e2e image", image, f64[0], f32[0])
-    _check("sky e2e dL_dalpha", rec.alpha.grad[0], f64[1], f32[1])
-    _check("sky e2e dL_dtexture", sky.texture.grad, f64[2], f32[2])
+    check_4x(image, f64[0], f32[0], "sky e2e image")
+    check_4x(rec.alpha.grad[0], f64[1], f32[1], "sky e2e dL_dalpha")
+    check_4x(sky.texture.grad, f64[2], f32[2], "sky e2e dL_dtexture")
     assert torch.equal(rec.color.grad, g)
     og = leaves["opacities"].grad
     assert torch.isfinite(og).all() and torch.count_nonzero(og) > 0

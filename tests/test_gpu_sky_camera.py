@@ -22,12 +22,11 @@ may be flagged.
 import ctypes
 import math
 
-import numpy as np
 import pytest
 import torch
 
 import gs_scenes
-import parity_report
+from gpu_checks import check_4x
 import sky_pose_ref
 from test_gpu_sky import CASES, _Recorder, _bits, _inputs
 
@@ -121,21 +120,6 @@ def _ref(name, with_alpha, device):
     return _REFS[key]
 
 
-def _check_4x(name, hip, f64, f32):
-    """max|hip - f64| <= 4 max|ref f32 - f64| + 1e-5 max|f64|; prints and records the figures"""
-    hip, f64, f32 = (np.asarray(t.detach().cpu(), np.float64) for t in (hip, f64, f32))
-    scale = np.abs(f64).max()
-    d32 = np.abs(f32 - f64).max()
-    bound = 4.0 * d32 + 1e-5 * scale
-    err = np.abs(hip - f64).max()
-    print(f"{name}: max|hip - f64| {err:.3e}  max|f32 - f64| {d32:.3e}  bound {bound:.3e}  "
-          f"used {err / bound if bound > 0 else 0.0:.3f}  max|f64| {scale:.3e}")
-    if scale > 0:
-        parity_report.record(name, hip, f64, 0.0, bound / scale)
-    assert np.isfinite(hip).all()
-    assert err <= bound, f"{name}: {err:.3e} > {bound:.3e}"
-
-
 def _zero_border(gv):
     z = torch.zeros(4, device=gv.device)
     return torch.equal(_bits(gv[3]), _bits(z)) and torch.equal(_bits(gv[:, 3]), _bits(z))
@@ -157,8 +141,8 @@ def test_matches_fp64_reference(name, with_alpha, tex_grad, device):
     assert (dtex is not None) == tex_grad
     assert _zero_border(gv)
     assert float(ref[torch.float64].abs().max()) > 0
-    _check_4x(f"sky {name} dL_dviewmatrix [{'alpha' if with_alpha else 'no alpha'}, {'tex' if tex_grad else 'no tex'}]",
-              gv[:3, :3], ref[torch.float64][:3, :3], ref[torch.float32][:3, :3])
+    check_4x(gv[:3, :3], ref[torch.float64][:3, :3], ref[torch.float32][:3, :3],
+             f"sky {name} dL_dviewmatrix [{'alpha' if with_alpha else 'no alpha'}, {'tex' if tex_grad else 'no tex'}]")
 
 
 # ---- 2. bit identities ----
@@ -419,7 +403,7 @@ def test_end_to_end_twist_with_sky(device):
                                   cam.projection_matrix.to(device, dtype))
         torch.autograd.backward(list(chain), list(gr))
         want.append(delta.grad)
-    _check_4x("ddelta [twist, sh2 + sky]", got, want[0], want[1])
+    check_4x(got, want[0], want[1], "ddelta [twist, sh2 + sky]")
 
     twist_r, image_r, _ = hip(False)
     assert torch.equal(_bits(image_r), _bits(image))

@@ -231,3 +231,56 @@ def test_dense_local_compositor_equals_dense():
         outs.append([img.detach(), m3.grad, m2.grad, op.grad, shs.grad, scl.grad, rot.grad])
     for a, b in zip(*outs):
         assert torch.allclose(a, b, rtol=1e-10, atol=1e-13)
+
+
+def _aux_anchor_scene(name):
+    """(cam, fp64 leaves, sh degree): the three Gaussians at 72x40 of the GPU tests' "empty-tile" scene, and 40
+    opaque, overlapping Gaussians at 48x32 (opacity 0.5 + 0.49 o, which stays below 0.99, so the first four
+    are set fully opaque: o G can then pass the 0.99 clamp, and three of them stacked stop a pixel)."""
+    if name == "empty-tile":
+        cam = gs_scenes.identity_camera(72, 40)
+        sc, deg = gs_scenes.random_gaussians(2000, 3, cam=gs_scenes.identity_camera(200, 120), seed=41), 3
+        sel = slice(0, 3)
+    else:
+        cam = gs_scenes.identity_camera(48, 32)
+        sc, deg = gs_scenes.random_gaussians(40, 1, cam=cam, seed=3, scale_range=(0.4, 1.2)), 1
+        sc.opacities = 0.5 + 0.49 * sc.opacities
+        sc.opacities[:4] = 1.0
+        sel = slice(None)
+    t = {k: getattr(sc, k)[sel].double() for k in ("means3D", "opacities", "shs", "scales", "rotations")}
+    return cam, t, deg
+
+
+def test_dense_local_aux_equals_dense_local():
+    """dense_ref_aux.render_local_aux against dense_ref.render_local in fp64, on both scenes: the same image,
+    radii and flag map bit for bit, alpha = 1 - T_final of the walk, and the inverse depth is render_local's
+    first channel for the colours (1 / tz, 0, 0) over a zero background."""
+    for name in ("empty-tile", "opaque"):
+        _aux_equals_local(name)
+
+
+def _aux_equals_local(name):
+    import dense_ref_aux
+
+    cam, t, deg = _aux_anchor_scene(name)
+    d, W, H = torch.float64, cam.image_width, cam.image_height
+    P = t["means3D"].shape[0]
+    args = (t["means3D"], torch.zeros((P, 3), dtype=d), t["opacities"], cam.world_view_transform.to(d),
+            cam.full_proj_transform.to(d), cam.camera_center.to(d), math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2),
+            W, H)
+    kw = dict(scales=t["scales"], rots=t["rotations"])
+    q = dense_ref._prep(*args, shs=t["shs"], deg=deg, **kw)
+    walk = dense_ref.walk_local(q, True)
+    clamped = sum(int((a_raw > 0.99).sum()) for _, _, _, _, a_raw, _, _, _ in walk)
+    if name == "opaque":  # otherwise the scene proves nothing about the clamp and the stop
+        assert int(walk.done.sum()) >= 1 and clamped >= 1, (int(walk.done.sum()), clamped)
+    bg = torch.tensor([0.2, 0.5, 0.1], dtype=d)
+    img, radii, flag = dense_ref.render_local(*args, bg, shs=t["shs"], deg=deg, **kw)
+    aimg, aradii, aflag, inv, alpha = dense_ref_aux.render_local_aux(*args, bg, shs=t["shs"], deg=deg, **kw)
+    assert torch.equal(aimg, img) and torch.equal(aradii, radii) and torch.equal(aflag, flag)
+    assert torch.equal(alpha, (1.0 - walk.T).reshape(1, H, W))
+    tz = q["tz"]
+    cols = torch.stack([1.0 / tz, torch.zeros_like(tz), torch.zeros_like(tz)], 1)
+    dimg, _, _ = dense_ref.render_local(*args, torch.zeros(3, dtype=d), colors=cols, **kw)
+    assert torch.equal(inv[0], dimg[0]) and float(inv.max()) > 0
+    assert not dimg[1:].any()
